@@ -12,8 +12,14 @@ device-side repack, once per step for all layers (`plan_build_us_per_step`).
 Contract: `python bench.py --gpus N --steps K --warmup W` prints ONE JSON line on
 rank 0.  For N > 1 launch with torch.distributed.run (one rank per GPU; `--gpus N` outside a
 launcher starts one); every rank decodes its own independent tree (weak scaling, no data-path
-collective), and BASELINE configs[4] -- the 8 N-tree forest sharded 8 per GPU by `shard_trees`
--- is measured in the same run (`cfg5_sharded_forest`).
+collective).
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, write the
+last step's outputs if `--dump-outputs DIR` is given, print the line.  `--full` adds everything
+else in the same run: stage-1 roofline and its ceiling, step percentiles, plan timing, the
+advancing-tree loops, the few-shot run, attention in situ, the other workloads, prefill, the CPU
+baseline and BASELINE configs[4] -- the 8 N-tree forest sharded 8 per GPU by `shard_trees`
+(`cfg5_sharded_forest`).  The `--no-*` options switch parts of a `--full` run off.
 """
 from __future__ import annotations
 
@@ -74,6 +80,7 @@ class Bench:
         self.v_new = torch.randn((layers, self.nq, self.Hkv * self.D), dtype=torch.float16, device=device, generator=g)
         leaves = [lf for t in self.forest.trees for lf in sorted(t.leaves.values(), key=lambda n: n.id)]
         loc = torch.tensor([lf.kv_indices[-1] for lf in leaves], dtype=torch.int32, device=device)
+        self.loc = loc
         self.updater = deft_amd.KVCacheUpdater(True, self.pool, loc, None, False)
         if w.mode == "seq":  # sequential comparator: every leaf attends to its own full path through the page table
             tree = self.forest.trees[0]
@@ -83,15 +90,14 @@ class Bench:
         else:
             self.meta = deft_amd.InputMetadata(mode, self.updater, self.pool)
         self.attn = [deft_amd.DeFTAttention(self.Hq, self.D, self.D ** -0.5, self.Hkv, l) for l in range(layers)]
-        self.out = None
+        self.out = self.outs = None
         self.graph = None
         self.launch = "eager"
 
     def step_eager(self):
-        o = None
-        for l in range(self.layers):
-            o = self.attn[l](self.q[l], self.k_new[l], self.v_new[l], self.meta)
-        self.out = o
+        # (every layer's output is kept: they are what a caller of the step receives, and `--dump-outputs` writes them)
+        self.outs = [self.attn[l](self.q[l], self.k_new[l], self.v_new[l], self.meta) for l in range(self.layers)]
+        self.out = self.outs[-1]
 
     def prepare(self, use_graph: bool = True):
         deft_amd.register_tree_metadata(self.md)
@@ -128,7 +134,7 @@ class Bench:
         """Drop the pools and the per-layer inputs (the scalars and the metadata stay): under a shared GPU -- eight gloo ranks on
         one device -- the headline's 6.7 GB must not sit beside the sharded forest's."""
         self.graph = None
-        self.forest = self.pool = self.q = self.k_new = self.v_new = self.updater = self.meta = self.attn = self.out = None
+        self.forest = self.pool = self.q = self.k_new = self.v_new = self.updater = self.meta = self.attn = self.out = self.outs = None
         torch.cuda.empty_cache()
 
     def algorithmic_bytes_per_layer(self) -> int:
@@ -545,6 +551,44 @@ def measure_traffic(args, kernel: str):
         shutil.rmtree(out, ignore_errors=True)
 
 
+DUMP_BYTES = 64_000_000  # all files of --dump-outputs together, .npy headers included
+DUMP_HEADER_ALLOWANCE = 4096  # per file, far above the 128 bytes numpy writes for these shapes
+
+
+def sample_rows(a, budget: int):
+    """`a` itself when it fits in `budget` bytes; otherwise a fixed, seeded sample of its rows (the leading two dimensions
+    flattened, rows kept in order), as many as fit.  The same shape always keeps the same rows."""
+    import numpy as np
+
+    if a.nbytes <= budget:
+        return a
+    rows = a.reshape(a.shape[0] * a.shape[1], *a.shape[2:])
+    keep = np.sort(np.random.default_rng(0).choice(rows.shape[0], budget // rows[0].nbytes, replace=False))
+    return rows[keep]
+
+
+def dump_outputs(b: Bench, out_dir: str):
+    """What the timed path computed in its last step, as float32 .npy files under `out_dir`:
+      attn_out.npy      [layers, nq, Hq*D]      every layer's DeFTAttention output
+      kv_appended.npy   [layers, nq, 2, Hkv, D] the K / V rows the step's fused append wrote into each layer's pool
+    Each file gets half of DUMP_BYTES; an array beyond its half keeps a fixed, seeded sample of its rows (`sample_rows`).  The
+    inputs are seeded, so two builds given the same arguments can be compared file for file."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize(b.device)
+    loc = b.loc.long()
+    arrays = {"attn_out": torch.stack([o.view(b.nq, -1) for o in b.outs]),
+              "kv_appended": torch.stack([b.pool.kv_data[l][loc] for l in range(b.layers)])}
+    budget = DUMP_BYTES // len(arrays) - DUMP_HEADER_ALLOWANCE
+    written = {}
+    for name, t in arrays.items():
+        a = sample_rows(t.float().cpu().numpy(), budget)
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+        written[name] = list(a.shape)
+    return written
+
+
 def gpu_state():
     """Clock / power mode of the GPU the numbers were taken on (state it)."""
     import shutil
@@ -716,6 +760,11 @@ def main():
                     help="set the process group up even at world size 1 (under a launcher: torch.distributed.run --nproc-per-node 1): "
                          "the N > 1 bracket -- init_process_group, barrier, MAX all-reduce on the control device -- on ONE GPU, which "
                          "is how RCCL itself gets exercised where no multi-GPU box is at hand")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything besides the headline in the same run (roofline, percentiles, plan timing, advancing-tree "
+                         "loops, few-shot run, in situ, other workloads, prefill, CPU baseline, sharded forest); off: the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32; rank 0)")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)  # the PMC child: timed steps only
     args = ap.parse_args()
 
@@ -764,6 +813,7 @@ def main():
         if w.mode == "flatten":
             b.time_stage1(reps=1)
         return
+    dumped = dump_outputs(b, args.dump_outputs) if args.dump_outputs and rank == 0 else None
     if args.in_situ_only:
         if rank == 0:
             print(json.dumps({"in_situ": in_situ(b), "attention_us_per_layer_back_to_back": round(ms_per_step * 1e3 / layers, 2)}), flush=True)
@@ -776,10 +826,49 @@ def main():
                               "note": "--step-only: the step graph alone (for kernel-trace statistics)"}), flush=True)
         return
 
+    algo = b.algorithmic_bytes_per_layer()
+    step_achieved = algo * layers / (dt / args.steps) / 1e9
+    line = None
+    if rank == 0:
+        Hq, Hkv, D, _ = GEOMETRY[w.model]
+        line = {
+            "metric": "tree_tokens_per_s", "value": round(tokens_per_s, 1), "unit": "tokens/s",
+            "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f16", "data": "synthetic",
+            "config": {"workload": f"{w.model} DeFT-{w.mode}, {w.kind} tree: {w.prefix}-token shared prefix x {w.width} "
+                                   f"branches x {w.branch_len} tokens, paged KV, {layers} layers "
+                                   f"(Hq={Hq}, Hkv={Hkv}, D={D}); {w.trees} independent tree(s) per GPU",
+                       "name": w.name, "queries": b.nq, "unique_kv_tokens": b.n_kv, "layers": layers,
+                       "blocks": int(b.md.block_q_cnts.shape[0]), "partial_rows": int(b.md.block_q.shape[0]),
+                       "launch": b.launch,
+                       "timed_region": "attention-only replay of ONE frozen decode step (hipGraph of 32 x (fused append, stage 1, "
+                                       "merge)); metadata / plan of that step are built before it; `end_to_end` (--full) is the "
+                                       "advancing-tree loop with them inside"},
+            "value_definition": "queries per step x n_gpus / (wall clock of the K timed steps / K): the steps are replayed back to "
+                                "back from one hipGraph between two device synchronisations (the driver's contract); "
+                                "`step_time_percentiles` (--full) brackets EVERY step with its own HIP event pair, which adds ~10 us "
+                                "of event work per step -- the wall-clock mean is the headline, the percentiles show the spread",
+            "attention_latency_us_per_step": round(ms_per_step * 1e3, 1),
+            "attention_latency_us_per_layer": round(ms_per_step * 1e3 / layers, 2),
+            "step_algorithmic_GBps": round(step_achieved, 1),
+            "step_hbm_frac": round(step_achieved / HBM_PEAK_GBPS, 4),
+            "metadata_build_ms": round(b.metadata_build_ms, 3),
+            "dist": ({"backend": args.dist_backend, "world_size": world, "ranks_share_gpus": bool(shared_gpus),
+                      "visible_gpus": torch.cuda.device_count()} if dist_on else None),
+            "outputs": ({"dir": args.dump_outputs, "arrays": dumped} if dumped is not None else None),
+        }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if dist_on:
+            import torch.distributed as dist
+
+            dist.destroy_process_group()
+        return
+
     s1 = b.time_stage1(reps=3)
     pct = b.step_percentiles(min(args.steps, 200))
     plan_us = b.time_plan()
-    algo = b.algorithmic_bytes_per_layer()
     roofline = None
     if s1 is not None:
         achieved = algo / (s1["mean_us"] * 1e-6) / 1e9
@@ -817,7 +906,6 @@ def main():
                     # the hardware ceiling of a launch of this size: a bare read of the same K/V bytes (deft_probe_stream_read)
                     "ceiling_us": ceil["us"], "ceiling_workgroups": ceil["workgroups"],
                     "launch_over_ceiling": round(s1["mean_us"] / ceil["us"], 3)}
-    step_achieved = algo * layers / (dt / args.steps) / 1e9
     e2e = None
     if rank == 0 and not dist_on and not args.no_e2e and w.trees == 1 and w.mode == "flatten":
         e2e = {"what": "the decode loop with the tree ADVANCING (one token per leaf and step, from the benchmarked tree on): "
@@ -994,37 +1082,13 @@ def main():
                         "cores": c16["cores"], "warmups": c16["warmups"], "reps": c16["reps"]}}
 
     if rank == 0:
-        Hq, Hkv, D, _ = GEOMETRY[w.model]
-        line = {
-            "metric": "tree_tokens_per_s", "value": round(tokens_per_s, 1), "unit": "tokens/s",
-            "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f16", "data": "synthetic",
-            "config": {"workload": f"{w.model} DeFT-{w.mode}, {w.kind} tree: {w.prefix}-token shared prefix x {w.width} "
-                                   f"branches x {w.branch_len} tokens, paged KV, {layers} layers "
-                                   f"(Hq={Hq}, Hkv={Hkv}, D={D}); {w.trees} independent tree(s) per GPU",
-                       "name": w.name, "queries": b.nq, "unique_kv_tokens": b.n_kv, "layers": layers,
-                       "blocks": int(b.md.block_q_cnts.shape[0]), "partial_rows": int(b.md.block_q.shape[0]),
-                       "launch": b.launch,
-                       "timed_region": "attention-only replay of ONE frozen decode step (hipGraph of 32 x (fused append, stage 1, "
-                                       "merge)); metadata / plan of that step are built before it; `end_to_end` below is the "
-                                       "advancing-tree loop with them inside"},
-            "value_definition": "queries per step x n_gpus / (wall clock of the K timed steps / K): the steps are replayed back to "
-                                "back from one hipGraph between two device synchronisations (the driver's contract); "
-                                "`step_time_percentiles` brackets EVERY step with its own HIP event pair, which adds ~10 us of "
-                                "event work per step -- the wall-clock mean is the headline, the percentiles show the spread",
-            "attention_latency_us_per_step": round(ms_per_step * 1e3, 1),
-            "attention_latency_us_per_layer": round(ms_per_step * 1e3 / layers, 2),
+        line.update({
             "step_time_percentiles": pct,
-            "step_algorithmic_GBps": round(step_achieved, 1),
-            "step_hbm_frac": round(step_achieved / HBM_PEAK_GBPS, 4),
-            "metadata_build_ms": round(b.metadata_build_ms, 3),
             "plan_build_us_per_step": round(plan_us, 1) if plan_us is not None else None,
             "end_to_end": e2e, "few_shot_run": few_shot_run, "in_situ": situ, "gpu_state": gpu_state(),
-            "dist": ({"backend": args.dist_backend, "world_size": world, "ranks_share_gpus": bool(shared_gpus),
-                      "visible_gpus": torch.cuda.device_count()} if dist_on else None),
             "roofline": roofline, "cpu_baseline": cpu, "cfg5_sharded_forest": cfg5, "prefill": prefill,
             "other_workloads": extras,
-        }
+        })
         print(json.dumps(line), flush=True)
     if dist_on:
         import torch.distributed as dist

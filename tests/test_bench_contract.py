@@ -1,17 +1,21 @@
-"""bench.py as the driver runs it (GPU box): the JSON contract of the default line, BASELINE configs[4] measured two ways in
-one run, and the N > 1 path -- launcher, process group, barrier / MAX bracket, sharded forest, its advancing loop -- rehearsed
-with two ranks on ONE GPU over gloo (`--dist-backend gloo`; the driver's 8-GPU run uses RCCL and one GPU per rank)."""
+"""bench.py as the driver runs it (GPU box): the JSON contract of the plain line and of `--dump-outputs`, BASELINE configs[4]
+measured two ways in one `--full` run, and the N > 1 path -- launcher, process group, barrier / MAX bracket, sharded forest, its
+advancing loop -- rehearsed with two ranks on ONE GPU over gloo (`--dist-backend gloo`; the driver's 8-GPU run uses RCCL and one
+GPU per rank)."""
 import json
 import os
 import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FAST = ["--no-extras", "--no-cpu-baseline", "--no-traffic", "--no-e2e"]
+FAST = ["--full", "--no-extras", "--no-cpu-baseline", "--no-traffic", "--no-e2e"]
+HEADLINE = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+            "dtype", "data", "config")
 
 
 def _line(cmd, timeout=900):
@@ -29,8 +33,7 @@ def test_cfg5_measured_two_ways_agrees_and_contract_keys():
     """`--workload forest_8kx8` (8 trees of 8192 x 8 x 64 in one pool, one Forest call per layer) as the HEADLINE, and the
     `cfg5_sharded_forest` line of the same run (shard_trees -> this rank's 8 trees): the same launches, so the same time."""
     d = _line([sys.executable, "bench.py", "--workload", "forest_8kx8", "--steps", "80", "--warmup", "10", *FAST])
-    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
-                "dtype", "data", "config", "roofline", "cpu_baseline"):
+    for key in (*HEADLINE, "roofline", "cpu_baseline"):
         assert key in d, key
     assert d["n_gpus"] == 1 and d["steps"] == 80 and d["warmup"] == 10 and d["scaling"] == "weak" and d["vs_baseline"] is None
     assert "workload" in d["config"] and "model" not in d["config"]
@@ -42,6 +45,34 @@ def test_cfg5_measured_two_ways_agrees_and_contract_keys():
     assert abs(c5["us_per_layer"] - head) / head < 0.08, (c5["us_per_layer"], head)
     assert abs(c5["tokens_per_s"] - d["value"]) / d["value"] < 0.08
     assert "error" not in (c5["end_to_end"] or {})
+
+
+def test_plain_run_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """No `--full`: the headline alone, over exactly `--steps` timed steps; `--dump-outputs` writes the last step's arrays as
+    float32 .npy, at most 64 MB in all (kv_appended, 33.5 MB whole, is a seeded sample of its rows), the same bits when the same
+    command runs again."""
+    cmd = [sys.executable, "bench.py", "--workload", "fewshot_1kx32", "--steps", "7", "--warmup", "2"]
+    a = _line(cmd + ["--dump-outputs", str(tmp_path / "a")])
+    b = _line(cmd + ["--dump-outputs", str(tmp_path / "b")])
+    for key in HEADLINE:
+        assert key in a, key
+    assert a["metric"] == "tree_tokens_per_s" and a["unit"] == "tokens/s" and a["higher_is_better"] is True and a["dtype"] == "f16"
+    assert a["steps"] == 7 and a["warmup"] == 2 and a["ms_per_step"] > 0 and a["value"] > 0
+    assert abs(a["value"] - a["config"]["queries"] / (a["ms_per_step"] * 1e-3)) / a["value"] < 1e-3
+    for key in ("roofline", "cpu_baseline", "cfg5_sharded_forest", "other_workloads", "end_to_end", "step_time_percentiles"):
+        assert key not in a, key
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["attn_out.npy", "kv_appended.npy"] and sorted(os.listdir(tmp_path / "b")) == names
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype == np.float32 and np.isfinite(x).all() and np.abs(x).max() > 0, n
+        assert np.array_equal(x, y), n
+        assert list(x.shape) == a["outputs"]["arrays"][n.split(".")[0]]
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 64_000_000
+    nq, layers = a["config"]["queries"], a["config"]["layers"]
+    assert np.load(tmp_path / "a" / "attn_out.npy").shape == (layers, nq, 32 * 128)  # 16.8 MB: whole
+    kv = np.load(tmp_path / "a" / "kv_appended.npy")
+    assert kv.shape == ((32_000_000 - 4096) // (2 * 32 * 128 * 4), 2, 32, 128) and kv.shape[0] < layers * nq
 
 
 def test_two_ranks_over_gloo_on_one_gpu():

@@ -12,8 +12,9 @@ ROOT=$(cd "$(dirname "$0")/.." && pwd)
 for rep in 1 2; do
 for tree in "$@"; do
   T=$(cd "$ROOT/$tree" 2>/dev/null && pwd || (cd "$tree" && pwd))
+  FULL=$(grep -qs -- '"--full"' $T/bench.py && echo --full)  # (the stage-1 column; a bench.py without --full measures it by default)
   for wl in $WLS; do
-    (cd $T && unset DEFT_AMD_LIB && PYTHONPATH=$T python bench.py --workload $wl $BENCH_EXTRA --no-cpu-baseline --no-extras --no-traffic --no-e2e --no-cfg5 --steps 100 2>/dev/null) |
+    (cd $T && unset DEFT_AMD_LIB && PYTHONPATH=$T python bench.py --workload $wl $BENCH_EXTRA $FULL --no-cpu-baseline --no-extras --no-traffic --no-e2e --no-cfg5 --steps 100 2>/dev/null) |
       python -c "import json,sys; d=json.loads(sys.stdin.read()); print('%-10s rep $rep  %-26s %7.2f  %s' % ('$tree', d['config']['name'], d['attention_latency_us_per_layer'], (d.get('roofline') or {}).get('avg_launch_us')))" 2>/dev/null || echo "$tree rep $rep $wl: failed"
   done
 done

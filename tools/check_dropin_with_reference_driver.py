@@ -10,7 +10,7 @@ reference's own objects (tests/golden/replay_*.npz, tools/gen_golden_replay.py).
 
 So this checks the class surface by USE, attribute by attribute (`node.children`, `node.refs`, `node.kv_indices`,
 `tree.leaves` order, `tree.leaf_to_req`, `pool.alloc` / `free` / `add_refs`, `req_to_token` ...), where tests/test_surface.py checks
-signatures.  tests/test_dropin_reference_driver.py runs it where /root/reference exists (this container) and skips elsewhere.
+signatures.  It needs a checkout of the reference beside the project, so it is run by hand, not by the test suite.
 
 Usage:  PYTHONDONTWRITEBYTECODE=1 python tools/check_dropin_with_reference_driver.py [NAME ...]
 """

@@ -28,12 +28,12 @@ timeout 300 python tools/replay.py --task speculative_decoding --modes node flat
 timeout 300 python tools/replay.py --task reasoning --modes flatten node --pipelined --legacy --out $O/${TAG}_replay_reasoning_tot50_pipelined_rebuild.json > $O/replay_totpl.log 2>&1
 timeout 300 python tools/replay.py --task reasoning --model llama3-8b --modes flatten --pipelined --out $O/${TAG}_replay_reasoning_tot50_llama3_pipelined.json > $O/replay_tot3p.log 2>&1
 timeout 300 python tools/replay.py --task reasoning --model llama3-8b --modes flatten --pipelined --legacy --out $O/${TAG}_replay_reasoning_tot50_llama3_pipelined_rebuild.json > $O/replay_tot3pl.log 2>&1
-timeout 900 python bench.py > $O/${TAG}_bench_default.json 2> $O/bench.err
+timeout 900 python bench.py --full > $O/${TAG}_bench_default.json 2> $O/bench.err
 # the N > 1 path on one GPU: two ranks over gloo (RCCL needs a GPU per rank; the driver's 8-GPU run uses it)
-timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --dist-backend gloo --steps 50 --warmup 10 --no-extras --no-cpu-baseline --no-traffic 2> $O/bench_2rank.err | grep '^{' > $O/${TAG}_bench_2rank_gloo_one_gpu.json
+timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --dist-backend gloo --steps 50 --warmup 10 --full --no-extras --no-cpu-baseline --no-traffic 2> $O/bench_2rank.err | grep '^{' > $O/${TAG}_bench_2rank_gloo_one_gpu.json
 # ... BASELINE configs[4] at its full rank count: eight ranks, 64 trees, all sharing this GPU over gloo; and RCCL itself at world size 1
-timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29518 bench.py --gpus 8 --dist-backend gloo --steps 10 --warmup 2 --no-extras --no-cpu-baseline --no-traffic --no-e2e 2> $O/bench_8rank.err | grep '^{' > $O/${TAG}_bench_8rank_gloo_one_gpu.json
-timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29519 bench.py --gpus 1 --force-dist --dist-backend nccl --steps 50 --warmup 10 --no-extras --no-cpu-baseline --no-traffic --no-e2e 2> $O/bench_rccl1.err | grep '^{' > $O/${TAG}_bench_rccl_world_size_1.json
+timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29518 bench.py --gpus 8 --dist-backend gloo --steps 10 --warmup 2 --full --no-extras --no-cpu-baseline --no-traffic --no-e2e 2> $O/bench_8rank.err | grep '^{' > $O/${TAG}_bench_8rank_gloo_one_gpu.json
+timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29519 bench.py --gpus 1 --force-dist --dist-backend nccl --steps 50 --warmup 10 --full --no-extras --no-cpu-baseline --no-traffic --no-e2e 2> $O/bench_rccl1.err | grep '^{' > $O/${TAG}_bench_rccl_world_size_1.json
 # what one cold launch of each BASELINE size can read (stand-alone probe; bench.py measures the same per workload as `ceiling_us`), and
 # the per-CU L2 -> LDS rate
 (cd tools/probes && make -s launch_ceiling l2_to_lds_bw) > /dev/null 2>&1
