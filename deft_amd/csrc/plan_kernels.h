@@ -517,7 +517,7 @@ __global__ __launch_bounds__(1024) void flatten_units_kernel(const int64_t* bloc
                 bits |= (!same_cnt[pd - 1] || any) ? (1 << (pd - 1)) : 0;
             }
             if (!(bits & 1)) bits = 0xe;  // not opening a run: longer periods read as "differs"
-            if (t >= NBreg) bits = ((t - NBreg) % win_tiles == 0) ? 0xf : 0xe;  // (overflow tiles: a run of their own per query chunk)
+            if (t >= NBreg) bits = (win_tiles > 0 && (t - NBreg) % win_tiles == 0) ? 0xf : 0xe;  // (overflow tiles: a run of their own per query chunk)
             // bit 4 (round 6, MHA): a FULL tile of ONE query.  A union group that would hold nothing but such tiles is not formed (phase
             // 1b): at branch lengths that are multiples of 128 every leaf tile is one, the launch ends with the eight-tile root chunks'
             // serial chains, and many one-tile items keep the other slots streaming until then where groups of three all start at

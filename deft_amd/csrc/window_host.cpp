@@ -21,6 +21,7 @@
 namespace deft {
 
 constexpr int WIN_REGIONS = 64;  // (window.h: hosting records a window plan's tables have room for)
+constexpr int WIN_OP_SLOTS = 1024;  // slots of one journal EXTEND the device replay takes (tree_plan.h TREE_OPS_NEW)
 
 struct WindowBooks {
     int nq = 0, n_nodes = 0, cap = 0, max_entries = 0, regions = 0;
@@ -199,7 +200,10 @@ int64_t deft_window_step(int64_t window, int replan, const int32_t* journal, int
     w->valid = false;  // (until this step's books are complete)
     for (int64_t at = 0; at + 2 < journal_words;) {
         const int op = journal[at], node = journal[at + 1], k = journal[at + 2];
-        if (node < 0 || node >= w->n_nodes || k < 0 || at + 3 + (op == 1 ? k : 0) > journal_words) return -1;
+        // (what tree_apply_ops refuses -- a RESET that carries slots, an EXTEND longer than it stages -- the books refuse too: the
+        // device tree stops at such an op, and books that went on would patch positions it never saw)
+        if (node < 0 || node >= w->n_nodes || k < 0 || k > WIN_OP_SLOTS || (op == 2 && k != 0) || at + 3 + (op == 1 ? k : 0) > journal_words)
+            return -1;
         if (op == 2) {  // RESET: the node's slots are dropped
             if (replan) {
                 w->clean[(size_t)node] = 1;

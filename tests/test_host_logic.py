@@ -596,3 +596,38 @@ def test_window_books_patch_lists():
     w = make(1, max_q_len=1)
     assert step(w, 1, [], [10, 11, 12]) == ([1, 1, 1], {(0, 0): (1, -1), (1, 0): (1, -2), (2, 0): (1, -3)})
     lib.deft_window_free(w)
+
+
+def test_window_books_refuse_the_journals_the_device_replay_refuses():
+    """The books and the device tree read the same journal: `tree_apply_ops` (csrc/tree_plan.h) sets error bit 4 and stops on a RESET
+    that carries slots (k != 0) and on an EXTEND of more than TREE_OPS_NEW = 1024 slots.  A window step that booked either would
+    patch positions the device tree never saw, so the step must not be expressible (-1: the caller replans) -- patch or replan."""
+    import ctypes as C
+
+    from deft_amd._lib import lib
+
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    leaf = np.asarray([1, 2, 3], dtype=np.int32)
+    refs = np.asarray([0b111, 0b001, 0b010, 0b100], dtype=np.uint64)
+    out = np.zeros(1 + 64 + 3 * 4096, dtype=np.int32)
+    loc = np.asarray([10, 11, 12], dtype=np.int32)
+
+    def step(w, replan, journal):
+        j = np.asarray(journal, dtype=np.int32)
+        return int(lib.deft_window_step(w, replan, ptr(j), len(journal), ptr(loc), ptr(out), out.size))
+
+    w = int(lib.deft_window_create(4, 3, 1, 16, ptr(leaf), ptr(refs), 32, 1, 4096))
+    assert w > 0
+    try:
+        # a RESET of a clean leaf with k = 0 is a patch step; the same op with k = 5 is what the device refuses
+        assert step(w, 1, [2, 1, 0]) > 0 and step(w, 0, [2, 1, 0]) > 0
+        assert step(w, 0, [2, 1, 5]) == -1
+        assert step(w, 1, [2, 1, 5]) == -1
+        # one EXTEND into the root: 1024 slots is the device's limit, 1025 and 1030 are past it (16 tiles per region: room for all)
+        ext = lambda k: [1, 0, k] + list(range(100, 100 + k))  # noqa: E731
+        assert step(w, 1, []) > 0 and step(w, 0, ext(1024)) > 0
+        assert step(w, 1, []) > 0 and step(w, 0, ext(1030)) == -1
+        assert step(w, 1, ext(1025)) == -1
+        assert step(w, 1, []) > 0  # (and a replan starts the books afresh)
+    finally:
+        lib.deft_window_free(w)

@@ -494,3 +494,170 @@ def test_sessions_hand_their_pinned_ring_on():
         gc.collect()
         assert any(r.data_ptr() == rings[-1] for have in S._PINNED_RINGS.values() for r, _ in have)
     assert rings[0] == rings[1] == rings[2] and sides[0] == sides[1] == sides[2]
+
+
+def _truth_check(outs, refs, tree, pool, q, Hq, Hkv, D, tag=None):
+    """Session outputs and eager outputs, every layer, against dense fp64 truth over the pool as it is AFTER the step (the fused
+    append has written the step's rows)."""
+    from truth import max_err, product_leaf_paths, tree_truth
+
+    paths = product_leaf_paths(tree)
+    n = len(paths)
+    for l, (out, ref) in enumerate(zip(outs, refs)):
+        truth = tree_truth(q[l, :n], pool.get_key_buffer(l), pool.get_value_buffer(l), paths, Hq, Hkv, D ** -0.5)
+        e_out, e_ref = max_err(out[:n], truth), max_err(ref, truth)
+        assert e_out < 5e-4 and e_ref < 5e-4, (tag, l, e_out, e_ref)
+
+
+# group sizes that do not divide 32: some query's G virtual rows straddle two 32-row passes (two regions of a window plan) --
+# G = 7 (Qwen2-7B's 28 / 4: query 4 is rows 28..34), 3 (query 10: rows 30..32), 5 (query 6: rows 30..34), 6 (query 5: rows 30..35)
+STRADDLING = [(28, 4), (24, 8), (10, 2), (12, 2)]
+# Values at a quarter: every leaf appends the SAME k / v row at every step, so after tens of steps its own tokens can carry most of its
+# attention and |o| reaches ~2 -- where one fp16 step of the output is 1e-3 and the correctly rounded result alone may sit 5e-4 from
+# fp64 truth.  Values at a quarter (exact in fp16) keep |o| < 0.5, and 5e-4 against truth measures the kernels, not the rounding.
+
+
+@pytest.mark.parametrize("mode", ["flatten", "node"])
+@pytest.mark.parametrize("heads", STRADDLING)
+def test_window_plans_with_query_groups_that_straddle_passes(heads, mode):
+    """test_session_equals_eager_step_for_step's loop at group sizes 7, 3, 5, 6: a straddling leaf's token takes a position in BOTH
+    regions of its rows (window_host.cpp `place` / `prev_new`), and the patch kernel's region table and the record kernels' per-pass
+    masks have to agree on it -- against the eager path and fp64 truth, through window replans and a structural change."""
+    Hq, Hkv = heads
+    D, layers, prefix, width = 128, 2, 700, 12
+    assert deft_amd.lib.deft_window_supported(width, 32, Hq, Hkv) == 1
+    g = torch.Generator(device="cuda").manual_seed(Hq * 31 + Hkv)
+    kv_init = torch.randn((layers, 4096, 2, Hkv, D), dtype=torch.float16, device="cuda", generator=g)
+    kv_init[:, :, 1] *= 0.25  # (values at a quarter: see above STRADDLING)
+    (te, pe), (ts, ps) = [_mk(Hkv, D, layers, prefix, width, 4096) for _ in range(2)]
+    for p in (pe, ps):
+        p._storage.copy_(kv_init)
+    cap = 16
+    q = torch.randn((layers, cap, Hq * D), dtype=torch.float16, device="cuda", generator=g)
+    k = torch.randn((layers, cap, Hkv * D), dtype=torch.float16, device="cuda", generator=g)
+    v = torch.randn((layers, cap, Hkv * D), dtype=torch.float16, device="cuda", generator=g) * 0.25
+    nq_now = [width]
+    sess = deft_amd.DecodeSession(ts, Hq, Hkv, D, layers, lambda l: (q[l, : nq_now[0]], k[l, : nq_now[0]], v[l, : nq_now[0]]), mode=mode,
+                                  incremental=True)
+    attn = [deft_amd.DeFTAttention(Hq, D, D ** -0.5, Hkv, l) for l in range(layers)]
+    fmode = deft_amd.forward_mode_from_cli(mode)
+
+    def both_steps(steps):
+        for s in range(steps):
+            for tree in (te, ts):
+                for leaf in tree.leaves.values():
+                    leaf.append_token(7)
+            upd = te.alloc()
+            md = deft_amd.TreeMetadata.from_tree_cache(te)
+            deft_amd.register_tree_metadata(md)
+            n = md.query_num
+            nq_now[0] = n
+            ref = [attn[l](q[l, :n], k[l, :n], v[l, :n], deft_amd.InputMetadata(fmode, upd, pe)) for l in range(layers)]
+            out = sess.step()
+            torch.cuda.synchronize()
+            for l in range(layers):
+                _agree(out[l][:n], ref[l], True, (s, l))
+            assert torch.equal(pe._storage, ps._storage)
+            assert torch.equal(te.req_to_token_pool.req_to_token, ts.req_to_token_pool.req_to_token)
+            _truth_check(out, ref, te, pe, q, Hq, Hkv, D, s)
+
+    both_steps(70)
+    assert sess.step_kinds["patch"] >= 50 and sess.step_kinds["replan"] >= 2 and sess.step_kinds["legacy"] == 0, sess.step_kinds
+    for tree in (te, ts):  # structural change: cut two leaves, branch one (14 queries: the straddling rows move)
+        lv = sorted(tree.leaves.values(), key=lambda n: n.id)
+        tree.cut(lv[1])
+        tree.cut(lv[4])
+        tree.branch(lv[0], 5)
+    both_steps(20)
+    assert sess.step_kinds["legacy"] == 0 and sess.device_errors() == 0, sess.step_kinds
+
+
+@pytest.mark.parametrize("mode", ["flatten", "node"])
+@pytest.mark.parametrize("heads", STRADDLING)
+def test_speculative_window_steps_with_query_groups_that_straddle_passes(heads, mode):
+    """test_session_speculative_decoding_steps_replay_one_graph's loop at group sizes 7, 3, 5, 6: a slot merged into the root takes an
+    entry in every region, and a reset straddling leaf refills both of its positions -- against the eager path and fp64 truth."""
+    Hq, Hkv = heads
+    D, layers, prefix, width = 128, 2, 500, 40
+    assert deft_amd.lib.deft_window_supported(width, 32, Hq, Hkv) == 1
+    g = torch.Generator(device="cuda").manual_seed(Hq * 17 + Hkv)
+    kv_init = torch.randn((layers, 4096, 2, Hkv, D), dtype=torch.float16, device="cuda", generator=g)
+    kv_init[:, :, 1] *= 0.25  # (values at a quarter: see above STRADDLING)
+    (te, pe), (ts, ps) = [_mk(Hkv, D, layers, prefix, width, 4096) for _ in range(2)]
+    for p in (pe, ps):
+        p._storage.copy_(kv_init)
+    q = torch.randn((layers, width, Hq * D), dtype=torch.float16, device="cuda", generator=g)
+    k = torch.randn((layers, width, Hkv * D), dtype=torch.float16, device="cuda", generator=g)
+    v = torch.randn((layers, width, Hkv * D), dtype=torch.float16, device="cuda", generator=g) * 0.25
+    sess = deft_amd.DecodeSession(ts, Hq, Hkv, D, layers, lambda l: (q[l], k[l], v[l]), mode=mode, incremental=True)
+    attn = [deft_amd.DeFTAttention(Hq, D, D ** -0.5, Hkv, l) for l in range(layers)]
+    fmode = deft_amd.forward_mode_from_cli(mode)
+    rng = np.random.default_rng(Hq + Hkv)
+    for step in range(40):
+        for tree in (te, ts):
+            for leaf in tree.leaves.values():
+                leaf.append_token(7)
+        upd = te.alloc()
+        md = deft_amd.TreeMetadata.from_tree_cache(te)
+        deft_amd.register_tree_metadata(md)
+        ref = [attn[l](q[l], k[l], v[l], deft_amd.InputMetadata(fmode, upd, pe)) for l in range(layers)]
+        out = sess.step()
+        torch.cuda.synchronize()
+        for l in range(layers):
+            _agree(out[l], ref[l], True, (step, l))
+        assert torch.equal(pe._storage, ps._storage)
+        _truth_check(out, ref, te, pe, q, Hq, Hkv, D, step)
+        accept = int(rng.integers(1, 5))
+        for tree in (te, ts):
+            lv = sorted(tree.leaves.values(), key=lambda n: n.id)
+            before = len(tree.root.kv_indices)
+            for lf in lv[:accept]:
+                tree.merge_nodes(tree.root, lf, pruneB_flag=False)
+            tree.reset_nodes_KV(lv, len(tree.root.kv_indices) - before)
+    assert sess.step_kinds["patch"] >= 30 and sess.step_kinds["legacy"] == 0, sess.step_kinds
+    assert sess.device_errors() == 0
+
+
+@pytest.mark.parametrize("width,window", [(128, True), (129, False)])
+def test_window_plans_at_the_edge_of_the_region_tables(width, window):
+    """16 query heads per KV head: 128 queries are 4 chunks x 16 passes = exactly the 64 regions a window plan's tables hold (window
+    steps run); 129 are one chunk more (the session falls back to the rebuild-every-step form) -- both against fp64 truth."""
+    Hq, Hkv, D, layers, prefix = 16, 1, 128, 1, 200
+    assert deft_amd.lib.deft_window_supported(width, 32, Hq, Hkv) == int(window)
+    g = torch.Generator(device="cuda").manual_seed(width)
+    kv_init = torch.randn((layers, 8192, 2, Hkv, D), dtype=torch.float16, device="cuda", generator=g)
+    trees = []
+    for _ in range(2):
+        req = deft_amd.ReqToTokenPool(256, 8192, device="cuda")
+        pool = deft_amd.TokenToKVPool(8192, torch.float16, Hkv, D, layers, device="cuda")
+        tree = deft_amd.TreeCache(torch.float16, Hkv, D, layers, req, pool, None, True, False)
+        tree.init_prompt(torch.arange(1, prefix + 1, dtype=torch.int32))
+        tree.branch(tree.root, width)
+        pool._storage.copy_(kv_init)
+        trees.append((tree, pool))
+    (te, pe), (ts, ps) = trees
+    q = torch.randn((layers, width, Hq * D), dtype=torch.float16, device="cuda", generator=g)
+    k = torch.randn((layers, width, Hkv * D), dtype=torch.float16, device="cuda", generator=g)
+    v = torch.randn((layers, width, Hkv * D), dtype=torch.float16, device="cuda", generator=g)
+    sess = deft_amd.DecodeSession(ts, Hq, Hkv, D, layers, lambda l: (q[l], k[l], v[l]))  # (incremental=True asked for)
+    attn = [deft_amd.DeFTAttention(Hq, D, D ** -0.5, Hkv, l) for l in range(layers)]
+    fmode = deft_amd.forward_mode_from_cli("flatten")
+    for step in range(12):
+        for tree in (te, ts):
+            for leaf in tree.leaves.values():
+                leaf.append_token(7)
+        upd = te.alloc()
+        md = deft_amd.TreeMetadata.from_tree_cache(te)
+        deft_amd.register_tree_metadata(md)
+        ref = [attn[0](q[0], k[0], v[0], deft_amd.InputMetadata(fmode, upd, pe))]
+        out = sess.step()
+        torch.cuda.synchronize()
+        _agree(out[0], ref[0], window, step)
+        assert torch.equal(pe._storage, ps._storage)
+        _truth_check(out, ref, te, pe, q, Hq, Hkv, D, step)
+    kinds = sess.step_kinds
+    if window:
+        assert kinds["patch"] >= 6 and kinds["legacy"] == 0, kinds
+    else:
+        assert kinds["legacy"] == 11 and kinds["patch"] == 0 and kinds["replan"] == 0, kinds
+    assert sess.device_errors() == 0

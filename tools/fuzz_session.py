@@ -39,7 +39,7 @@ def agree(out, ref, inc, tag):
 
 
 while time.time() < t_end:
-    Hq, Hkv = rng.choice([(32, 32), (32, 8), (8, 2), (4, 4), (16, 1)])
+    Hq, Hkv = rng.choice([(32, 32), (32, 8), (8, 2), (4, 4), (16, 1), (28, 4), (24, 8)])
     # (head_dim 64 -- head pairs on the tile-parallel kernel -- where the geometry allows it: an even number of KV heads)
     D, layers = (64 if Hkv % 2 == 0 and rng.random() < 0.25 else 128), rng.choice([1, 2])
     mode = rng.choice(["flatten", "flatten", "node", "node_chunk"])
