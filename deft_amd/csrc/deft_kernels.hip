@@ -2155,7 +2155,7 @@ int deft_window_patch(int n_nodes, int nq, int nqw, const int32_t* node_start, i
     }
     TreeDev t{n_nodes, nq, nqw, node_start, node_len, node_cap, reinterpret_cast<const unsigned long long*>(refs), leaf_node, slots};
     WindowPatch w{ops, cache_loc, patch, win_tab, static_cast<char*>(plan) + PLAN_HDR, static_cast<int32_t*>(scratch) + TREE_ERR,
-                  max_q_len, Hq / Hkv, win_tiles, kv_stride_slot, new_stride_tok * 2};
+                  static_cast<const int32_t*>(scratch) + WIN_DIM_PAD, max_q_len, Hq / Hkv, win_tiles, kv_stride_slot, new_stride_tok * 2};
     if (fetch_ring && (!fetch_dst || !fetch_counter || fetch_slot_bytes < 32 || fetch_slot_bytes % 16 || fetch_ring_n < 1)) {
         set_error("deft_window_patch: bad fetch arguments");
         return DEFT_EINVAL;

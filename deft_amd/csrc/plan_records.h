@@ -14,7 +14,7 @@ typedef short short4v __attribute__((ext_vector_type(4)));
 // group), g fastest.  A tile whose cnt * G rows exceed 32 appears once per 32-row pass; passes of a run
 // of tiles with one query list are ordered pass-major so that consecutive records fold.
 constexpr int PLAN_BYTES = 2048;
-constexpr int PLAN_ROWOFF = 0;   // int64[128]  byte offset of each slot's row in the pool (pads alias slot 0)
+constexpr int PLAN_ROWOFF = 0;   // int64[128]  byte offset of each slot's row in the pool (pads alias the tile's first slot)
 constexpr int PLAN_MASK = 1024;  // uint32[128] bit v set <=> virtual row v sees the slot (0 for pads)
 constexpr int PLAN_DESC = 1536;  // int32[8]    n_vrows, prow, opens_run, run_id, chunk tiles (0 = follower), first follower record,
                                  //             temporal (the tile is folded by so many passes that its rows should stay in L2), -
@@ -33,6 +33,7 @@ constexpr int HDR_QLISTS = 3;
 constexpr int WIN_PASSES = 16;   // 32-row passes per query chunk the table has room for (max_q_len * G / 32)
 constexpr int WIN_DIM_NB = 10;   // dims[10]: blocks (Flatten) / entries (Node) in front of the overflow ones
 constexpr int WIN_DIM_P = 11;    // dims[11]: block_q / node_q elements in front of the overflow lists
+constexpr int WIN_DIM_PAD = 12;  // dims[12]: the live slot that overflow positions without a key alias (window.h)
 
 // 64 lanes x 16 bytes, global (per-lane address) -> LDS (lds_dst + 16*lane).  M0 is not
 // otherwise used by the kernels (checked in the .s), so it is written, not saved.

@@ -32,16 +32,27 @@ namespace deft {
 
 constexpr int WIN_ERR = 8;       // dims[TREE_ERR] bit: the overflow blocks do not fit the arrays' capacities
 
+// An overflow position that holds no key -- not given out yet, or cleared by a RESET -- is still READ by stage 1 (its mask is 0:
+// P = 0, but 0 x V = NaN when the row holds NaN or Inf, and unused pool slots may).  So it aliases a slot that is on a live path
+// for the whole window: the first slot of the exact plan's first block / entry (the static part of the plan keeps its slots
+// until the next replan: window_host.cpp refuses a RESET of a node it still holds).  dims[WIN_DIM_PAD] keeps it for the patches.
+// The exact plan holds no key (NB / KV = 0; the pad falls back to slot 0) only for a tree without a single key in front of the step:
+// a session's epoch starts with an upload step that gives every leaf a key, so a replan finds at least the prompt's keys or those --
+// unless the caller has reset every node of a tree without a prompt.
+
 // Flatten: append ceil(nq / max_q_len) * win_tiles overflow blocks behind this step's blocks (dims[5], dims[6]).
 __global__ __launch_bounds__(256) void window_blocks_kernel(TreeMdOut o, int32_t* dims, int nq, int max_q_len, int win_tiles,
                                                             int block_len, int nb_cap, int p_cap) {
     __shared__ int sNB, sP;
+    __shared__ int64_t sPad;
     if (threadIdx.x == 0) {
         sNB = dims[5];
         sP = dims[6];
+        sPad = sNB > 0 ? o.block_kv[0] : 0;  // (block 0's position 0 always holds a key)
     }
     __syncthreads();
     const int NB = sNB, P = sP;
+    const int64_t pad = sPad;
     const int chunks = (nq + max_q_len - 1) / max_q_len;
     const int nblk = chunks * win_tiles;
     if (dims[TREE_ERR]) return;
@@ -56,7 +67,7 @@ __global__ __launch_bounds__(256) void window_blocks_kernel(TreeMdOut o, int32_t
         const int p0 = P + c * win_tiles * max_q_len + j * cnt;  // (every chunk in front of c is full)
         for (int i = threadIdx.x; i < cnt; i += blockDim.x) o.block_q[p0 + i] = c * max_q_len + i;
         for (int k = threadIdx.x; k < block_len; k += blockDim.x) {
-            o.block_kv[(int64_t)t * block_len + k] = 0;  // (a valid slot: masked rows are still requested)
+            o.block_kv[(int64_t)t * block_len + k] = pad;  // (a live slot: masked rows are still requested)
             o.block_bitmasks[(int64_t)t * block_len + k] = 0;
         }
         if (threadIdx.x == 0) {
@@ -68,6 +79,7 @@ __global__ __launch_bounds__(256) void window_blocks_kernel(TreeMdOut o, int32_t
     if (threadIdx.x == 0) {
         dims[WIN_DIM_NB] = NB;
         dims[WIN_DIM_P] = P;
+        dims[WIN_DIM_PAD] = (int32_t)pad;
         dims[5] = NB + nblk;
         dims[6] = P + win_tiles * nq;
         dims[7] = (NB + nblk) * block_len;
@@ -78,13 +90,16 @@ __global__ __launch_bounds__(256) void window_blocks_kernel(TreeMdOut o, int32_t
 __global__ __launch_bounds__(256) void window_entries_kernel(TreeMdOut o, int32_t* dims, int nq, int max_q_len, int win_tiles,
                                                              int ne_cap, int q_cap, int kv_cap) {
     __shared__ int sNE, sQ, sKV;
+    __shared__ int64_t sPad;
     if (threadIdx.x == 0) {
         sNE = dims[1];
         sQ = dims[3];
         sKV = dims[4];
+        sPad = sKV > 0 ? o.node_kv[0] : 0;  // (the first entry's first slot)
     }
     __syncthreads();
     const int NE = sNE, Q = sQ, KV = sKV;
+    const int64_t pad = sPad;
     const int chunks = (nq + max_q_len - 1) / max_q_len;
     const int len = win_tiles * TILE;
     if (dims[TREE_ERR]) return;
@@ -95,7 +110,7 @@ __global__ __launch_bounds__(256) void window_entries_kernel(TreeMdOut o, int32_
     for (int c = 0; c < chunks; ++c) {
         const int cnt = min(max_q_len, nq - c * max_q_len);
         for (int i = threadIdx.x; i < cnt; i += blockDim.x) o.node_q[Q + c * max_q_len + i] = c * max_q_len + i;
-        for (int k = threadIdx.x; k < len; k += blockDim.x) o.node_kv[KV + (int64_t)c * len + k] = 0;
+        for (int k = threadIdx.x; k < len; k += blockDim.x) o.node_kv[KV + (int64_t)c * len + k] = pad;
         if (threadIdx.x == 0) {
             o.node_q_len[NE + c] = cnt;
             o.node_kv_len[NE + c] = len;
@@ -106,6 +121,7 @@ __global__ __launch_bounds__(256) void window_entries_kernel(TreeMdOut o, int32_
     if (threadIdx.x == 0) {
         dims[WIN_DIM_NB] = NE;
         dims[WIN_DIM_P] = Q;
+        dims[WIN_DIM_PAD] = (int32_t)pad;
         dims[1] = NE + chunks;
         dims[3] = Q + nq;
         dims[4] = KV + chunks * len;
@@ -159,6 +175,7 @@ struct WindowPatch {
     const int32_t* tab;        // [chunk][WIN_PASSES][2]: leader record, first follower record (the record kernels write it)
     char* records;             // plan records
     int32_t* err;              // dims + TREE_ERR
+    const int32_t* pad;        // dims + WIN_DIM_PAD: the live slot a cleared position (row mask 0) aliases
     int max_q_len, G, win_tiles;
     int64_t kv_stride_slot;    // elements
     int64_t new_row_bytes;
@@ -253,9 +270,11 @@ __global__ __launch_bounds__(1024) void window_patch_kernel(TreeDev t, WindowPat
     // ---- the plan: one thread per entry ------------------------------------------------------------------------------------
     const int NH = sNH;
     const int32_t* ent = w.patch + 1 + WIN_REGIONS;
+    const int pad = *w.pad;
     for (int e = tid; e < n_ent; e += 1024) {
-        const int key = ent[3 * e], val = ent[3 * e + 2];
+        const int key = ent[3 * e];
         const uint32_t mask = (uint32_t)ent[3 * e + 1];
+        const int val = mask ? ent[3 * e + 2] : pad;  // (a cleared position: no row sees it, but it is read)
         const int hi = key >> 20, pos = key & 0xfffff;
         const int j = pos >> 7, k = pos & (TILE - 1);
         if (hi < 0 || hi >= NH || j >= w.win_tiles) {

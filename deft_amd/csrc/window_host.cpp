@@ -210,7 +210,8 @@ int64_t deft_window_step(int64_t window, int replan, const int32_t* journal, int
             } else {
                 if (!w->clean[(size_t)node]) return -1;
                 const auto& o = w->own[(size_t)node];
-                for (int i = 0; i < w->live[(size_t)node]; ++i) w->put(o[(size_t)i], 0, 0);  // (no row sees the position: cleared)
+                // (no row sees the position: cleared -- window_patch_kernel points a row mask of 0 at the window's live pad slot)
+                for (int i = 0; i < w->live[(size_t)node]; ++i) w->put(o[(size_t)i], 0, 0);
                 w->live[(size_t)node] = 0;
             }
             at += 3;
