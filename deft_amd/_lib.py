@@ -109,6 +109,49 @@ lib.deft_kv_append_f16.restype = C.c_int
 lib.deft_flatten_read_partials.argtypes = [_vp, _sz] + [_i32] * 6 + [_vp, _vp, _vp]
 lib.deft_flatten_read_partials.restype = C.c_int
 
+# Every data entry point exists for both element types (include/deft_amd.h): the _bf16 twin takes its _f16 sibling's arguments.
+ELEM_ENTRY_POINTS = (
+    "deft_flatten_decode", "deft_flatten_decode_append", "deft_flatten_decode_rope_append", "deft_flatten_stage1",
+    "deft_node_decode", "deft_node_decode_append", "deft_node_decode_rope_append",
+    "deft_seq_decode", "deft_seq_decode_append", "deft_kv_append", "deft_rope_qk", "deft_prefill",
+)
+for _f in ELEM_ENTRY_POINTS:
+    if hasattr(lib, _f + "_bf16"):  # (DEFT_AMD_LIB may name an older build for an A/B of fp16: it has no twins, and `entry` says so)
+        getattr(lib, _f + "_bf16").argtypes = getattr(lib, _f + "_f16").argtypes
+        getattr(lib, _f + "_bf16").restype = C.c_int
+
+_SUFFIX = {torch.float16: "_f16", torch.bfloat16: "_bf16"}
+ELEM_DTYPES = tuple(_SUFFIX)
+
+
+def elem_suffix(dtype, what: str = "tensors") -> str:
+    """"_f16" / "_bf16": the entry-point suffix of an element type.  Anything else is a TypeError: there is no other path."""
+    try:
+        return _SUFFIX[dtype]
+    except KeyError:
+        raise TypeError(f"{what} must be float16 or bfloat16, got {dtype}") from None
+
+
+def same_elem_dtype(**tensors) -> torch.dtype:
+    """The one element type of q, pool, new rows and output; a mixed call must not run."""
+    items = list(tensors.items())
+    dtype = items[0][1].dtype
+    elem_suffix(dtype, items[0][0])
+    for name, t in items[1:]:
+        if t.dtype != dtype:
+            raise TypeError(f"{name} is {t.dtype} but {items[0][0]} is {dtype}: q, the KV pool, the new rows and the output "
+                            "must share one element type")
+    return dtype
+
+
+def entry(name: str, dtype):
+    """(function, its name) of data entry point `name` ("deft_flatten_decode", ...) for an element type."""
+    full = name + elem_suffix(dtype)
+    if not hasattr(lib, full):
+        raise DeftLibraryError(f"{LIB_PATH} does not export {full}: a build from before the bfloat16 entry points")
+    return getattr(lib, full), full
+
+
 lib.deft_md_build.argtypes = [_i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32]
 lib.deft_md_build.restype = _i64
 lib.deft_md_sizes.argtypes = [_i64, _vp]
@@ -177,7 +220,7 @@ EXPORTED = (
     "deft_prefill_f16", "deft_rope_qk_f16", "deft_seq_plan_bytes", "deft_seq_workspace_bytes", "deft_seq_build_plan", "deft_seq_decode_f16", "deft_seq_decode_append_f16",
     "deft_kv_append_f16", "deft_probe_stream_read", "deft_md_build", "deft_md_sizes", "deft_md_fetch", "deft_md_free",
     "deft_tree_create",
-) + tuple(_TREE_FUNCS)
+) + tuple(_f + "_bf16" for _f in ELEM_ENTRY_POINTS) + tuple(_TREE_FUNCS)
 
 _ERR_NAMES = {-1: "DEFT_EINVAL", -2: "DEFT_EUNSUPPORTED", -3: "DEFT_EHIP", -4: "DEFT_EWORKSPACE"}
 

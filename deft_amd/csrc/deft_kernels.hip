@@ -14,23 +14,24 @@
 //   * K and V rows are gathered through the slot list into LDS with 16-byte
 //     per-lane loads (16 lanes cover one 256-byte row).  K is stored with an XOR
 //     swizzle of its 16-byte chunks so the MFMA A-fragment reads are conflict-free.
-//   * S^T = K Q^T on v_mfma_f32_32x32x16_f16: keys are the M dimension, so K
+//   * S^T = K Q^T on v_mfma_f32_32x32x16_f16 / _bf16: keys are the M dimension, so K
 //     fragments are 16-byte row pieces straight from LDS and Q fragments are
 //     16-byte row pieces straight from global memory; each lane ends up holding
 //     16 key scores of ONE query, so the row max / row sum are in-lane reductions
 //     plus one cross-half shuffle and a 4-wave exchange through LDS.
-//   * P (fp16) goes through LDS once; O^T = V^T P^T on the same MFMA, each wave
+//   * P (rounded once to the element type, fp16 or bf16) goes through LDS once; O^T = V^T P^T on the same MFMA, each wave
 //     producing 32 of the D output columns for all 32 queries.
 //   * Node mode reuses the same kernel: a prep kernel cuts every node entry into
 //     128-slot tiles (all queries of the entry see all slots), which removes the
 //     reference's serial walk over long nodes.
 //   * the merge is a deterministic gather (no atomics): true max, fp32 accumulate,
-//     one fp16 rounding.
+//     one rounding to the element type.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 #include "common.h"
 
@@ -43,6 +44,42 @@ typedef float floatx16 __attribute__((ext_vector_type(16)));
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 typedef float floatx2 __attribute__((ext_vector_type(2)));
 typedef uint32_t uintx4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+
+// One 16-bit element of q, the K/V pool, the new rows and the output: IEEE binary16 or bfloat16.  Host code and parameter
+// structs only ever ADDRESS elements (strides are in elements, both kinds are two bytes); what an element means is a
+// compile-time parameter of every kernel that does arithmetic on one, carried by the traits below.  Partials,
+// log-sum-exps, the merge and every plan are fp32 / integers and do not depend on it.
+typedef uint16_t e16;
+
+// Element traits: scalar and vector types, the matrix instruction, and the two conversions.  from_float rounds to nearest
+// even ONCE in both kinds (v_cvt_f16_f32 / v_cvt_pk_bf16_f32); to_float is exact.
+struct F16 {
+    using scalar = _Float16;
+    using vec8 = half8;
+    using vec4 = half4;
+    using vec2 = half2v;
+    static __device__ __forceinline__ floatx16 mfma(vec8 a, vec8 b, floatx16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
+    static __device__ __forceinline__ float to_float(scalar x) { return (float)x; }
+    static __device__ __forceinline__ scalar from_float(float x) { return (_Float16)x; }
+    static __device__ __forceinline__ vec8 neg(vec8 x) { return -x; }
+};
+struct BF16 {
+    using scalar = __bf16;
+    using vec8 = bf16x8;
+    using vec4 = bf16x4;
+    using vec2 = bf16x2;
+    static __device__ __forceinline__ floatx16 mfma(vec8 a, vec8 b, floatx16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
+    static __device__ __forceinline__ float to_float(scalar x) { return (float)x; }
+    static __device__ __forceinline__ scalar from_float(float x) { return (__bf16)x; }
+    static __device__ __forceinline__ vec8 neg(vec8 x) {  // the sign bit of each element: no round trip through fp32
+        uintx4 u = __builtin_bit_cast(uintx4, x);
+        u ^= 0x80008000u;
+        return __builtin_bit_cast(vec8, u);
+    }
+};
 
 constexpr int TILE = DEFT_BLOCK_LEN;  // 128 KV slots per tile
 constexpr int MQ = DEFT_MAX_Q_LEN;    // 32 query rows per tile
@@ -50,10 +87,10 @@ constexpr float LOG2E = 1.4426950408889634f;
 constexpr float LN2 = 0.6931471805599453f;
 
 struct Stage1Params {
-    const _Float16* q;
+    const e16* q;
     int64_t q_st, q_sh;
-    const _Float16* k;
-    const _Float16* v;
+    const e16* k;
+    const e16* v;
     int64_t kv_ss, kv_sh;
     // Flatten sources (MODE 0)
     const int64_t* block_q;
@@ -95,16 +132,19 @@ struct Stage1Smem {
 // ---------------------------------------------------------------------------
 // stage 1
 // ---------------------------------------------------------------------------
-template <int D, int MODE>
+template <class T, int D, int MODE>
 __global__ __launch_bounds__(256, 2) void stage1_kernel(Stage1Params p) {
+    using scalar = typename T::scalar;
+    using vec8 = typename T::vec8;
+    using vec4 = typename T::vec4;
     constexpr int CH = D / 8;    // 16-byte chunks per K/V row
     constexpr int KS = D / 16;   // MFMA k-steps of S^T = K Q^T
     constexpr int MB = (D + 31) / 32;  // 32-column output blocks of O^T (head_dim 16: one block, half of it unused)
     using SM = Stage1Smem<D>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    _Float16* sK = reinterpret_cast<_Float16*>(smem + SM::K_OFF);
-    _Float16* sV = reinterpret_cast<_Float16*>(smem + SM::V_OFF);
-    _Float16* sP = reinterpret_cast<_Float16*>(smem + SM::P_OFF);
+    scalar* sK = reinterpret_cast<scalar*>(smem + SM::K_OFF);
+    scalar* sV = reinterpret_cast<scalar*>(smem + SM::V_OFF);
+    scalar* sP = reinterpret_cast<scalar*>(smem + SM::P_OFF);
     uint32_t* sMask = reinterpret_cast<uint32_t*>(smem + SM::MASK_OFF);
     float* sWmax = reinterpret_cast<float*>(smem + SM::WMAX_OFF);
     float* sWsum = reinterpret_cast<float*>(smem + SM::WSUM_OFF);
@@ -184,13 +224,13 @@ __global__ __launch_bounds__(256, 2) void stage1_kernel(Stage1Params p) {
         const int hq = kvh * p.G + g;
 
         // ---- Q fragments (B operand of S^T): 8 halfs of query row c per k-step ----
-        half8 qf[KS];
+        vec8 qf[KS];
         {
-            const _Float16* qp = p.q + qrow * p.q_st + (int64_t)hq * p.q_sh + 8 * h;
+            const e16* qp = p.q + qrow * p.q_st + (int64_t)hq * p.q_sh + 8 * h;
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
-                half8 z = {0, 0, 0, 0, 0, 0, 0, 0};
-                qf[ks] = qvalid ? *reinterpret_cast<const half8*>(qp + 16 * ks) : z;
+                vec8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+                qf[ks] = qvalid ? *reinterpret_cast<const vec8*>(qp + 16 * ks) : z;
             }
         }
         __syncthreads();  // K/V/masks staged (g == 0); sP / sWmax / sWsum free again (g > 0)
@@ -201,12 +241,12 @@ __global__ __launch_bounds__(256, 2) void stage1_kernel(Stage1Params p) {
         for (int r = 0; r < 16; ++r) acc[r] = 0.f;
         {
             const int key = 32 * w + c;
-            const _Float16* krow = sK + key * D;
+            const scalar* krow = sK + key * D;
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
                 const int pos = (2 * ks + h) ^ (key & (CH - 1));
-                const half8 a = *reinterpret_cast<const half8*>(krow + pos * 8);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, qf[ks], acc, 0, 0, 0);
+                const vec8 a = *reinterpret_cast<const vec8*>(krow + pos * 8);
+                acc = T::mfma(a, qf[ks], acc);
             }
         }
         // acc[r] = S^T[key = 32w + (r&3) + 8*(r>>2) + 4h][query = c]
@@ -231,20 +271,20 @@ __global__ __launch_bounds__(256, 2) void stage1_kernel(Stage1Params p) {
         const float m = fmaxf(fmaxf(sWmax[c], sWmax[MQ + c]), fmaxf(sWmax[2 * MQ + c], sWmax[3 * MQ + c]));
         const float msafe = (m == -INFINITY) ? 0.f : m;
 
-        // ---- P = exp2(s - m) as fp16, row sums of the ROUNDED values -------------------
+        // ---- P = exp2(s - m) rounded once to the element type, row sums of the ROUNDED values -------------------
         float sum = 0.f;
 #pragma unroll
         for (int g4 = 0; g4 < 4; ++g4) {
-            half4 p4;
+            vec4 p4;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const _Float16 ph = (_Float16)exp2f(s[4 * g4 + i] - msafe);
+                const scalar ph = T::from_float(exp2f(s[4 * g4 + i] - msafe));
                 p4[i] = ph;
-                sum += (float)ph;
+                sum += T::to_float(ph);
             }
             // keys 32w + 8*g4 + 4h + (0..3) of query row c; 16-byte chunks XOR-swizzled by row
             const int pos = (4 * w + g4) ^ (c & 15);
-            *reinterpret_cast<half4*>(sP + c * TILE + pos * 8 + 4 * h) = p4;
+            *reinterpret_cast<vec4*>(sP + c * TILE + pos * 8 + 4 * h) = p4;
         }
         sum += __shfl_xor(sum, 32);
         if (h == 0) sWsum[w * MQ + c] = sum;
@@ -255,15 +295,15 @@ __global__ __launch_bounds__(256, 2) void stage1_kernel(Stage1Params p) {
             floatx16 o;
 #pragma unroll
             for (int r = 0; r < 16; ++r) o[r] = 0.f;
-            const _Float16* vcol = sV + 32 * w + c;
-            const _Float16* prow_p = sP + c * TILE;
+            const scalar* vcol = sV + 32 * w + c;
+            const scalar* prow_p = sP + c * TILE;
 #pragma unroll
             for (int ks = 0; ks < TILE / 16; ++ks) {
-                half8 a;
+                vec8 a;
 #pragma unroll
-                for (int j = 0; j < 8; ++j) a[j] = (32 * w + c < D) ? vcol[(16 * ks + 8 * h + j) * D] : (_Float16)0.f;
-                const half8 b = *reinterpret_cast<const half8*>(prow_p + (((2 * ks + h) ^ (c & 15)) * 8));
-                o = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, o, 0, 0, 0);
+                for (int j = 0; j < 8; ++j) a[j] = (32 * w + c < D) ? vcol[(16 * ks + 8 * h + j) * D] : (scalar)0.f;
+                const vec8 b = *reinterpret_cast<const vec8*>(prow_p + (((2 * ks + h) ^ (c & 15)) * 8));
+                o = T::mfma(a, b, o);
             }
             // o[r] = O^T[d = 32w + (r&3) + 8*(r>>2) + 4h][query = c]
             const float lsum = sWsum[c] + sWsum[MQ + c] + sWsum[2 * MQ + c] + sWsum[3 * MQ + c];
@@ -349,9 +389,9 @@ __global__ __launch_bounds__(256) void node_prep_kernel(const int64_t* node_kv_o
 // that a head is merged on the XCD whose L2 holds its partial rows.
 // ---------------------------------------------------------------------------
 constexpr int MERGE_LIST_CAP = 4096;  // row ids per wave in LDS; longer lists are merged window by window
-template <int D>
+template <class T, int D>
 __global__ __launch_bounds__(256) void merge_kernel(const float* partial_o, const float* partial_lse, const int32_t* row_q,
-                                                     int64_t rows, _Float16* out, int64_t o_st, int64_t o_sh, int Hq, int cap,
+                                                     int64_t rows, e16* out, int64_t o_st, int64_t o_sh, int Hq, int cap,
                                                      int lists, const int32_t* qoff, const int32_t* qlist, const int32_t* qinl,
                                                      int nq_total, int hgroup) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -369,14 +409,14 @@ __global__ __launch_bounds__(256) void merge_kernel(const float* partial_o, cons
     const int hq = (bx % ng) * hgroup + bx / ng;
     const int q = blockIdx.y * 4 + w;
     if (q >= nq_total) return;
-    _Float16* out_q = out + (int64_t)q * o_st;
+    e16* out_q = out + (int64_t)q * o_st;
     int* list = reinterpret_cast<int*>(smem) + w * cap;
 #ifdef DEFT_EXPERIMENTS
     if (lists >= 2) {  // TIMING ONLY (wrong results): row ids computed, not loaded -- what a merge without its first dependent round trip costs
         const int n = lists - 1;
         if (lane < n) list[lane] = (int)(((int64_t)q * n + lane) % rows);
         __builtin_amdgcn_wave_barrier();
-        merge_heads_wave<D, 0, 1>(partial_o, partial_lse, row_q, rows, q, hq, 1, Hq, list, cap, n, out_q, o_sh, lane);
+        merge_heads_wave<T, D, 0, 1>(partial_o, partial_lse, row_q, rows, q, hq, 1, Hq, list, cap, n, out_q, o_sh, lane);
         return;
     }
 #endif
@@ -386,22 +426,22 @@ __global__ __launch_bounds__(256) void merge_kernel(const float* partial_o, cons
         if (n <= 15 && n <= cap) {
             if (lane >= 1 && lane <= n) list[lane - 1] = mine;
             __builtin_amdgcn_wave_barrier();
-            merge_heads_wave<D, 0, 1>(partial_o, partial_lse, row_q, rows, q, hq, 1, Hq, list, cap, n, out_q, o_sh, lane);
+            merge_heads_wave<T, D, 0, 1>(partial_o, partial_lse, row_q, rows, q, hq, 1, Hq, list, cap, n, out_q, o_sh, lane);
         } else if (n <= cap) {  // a longer list: the query's stretch of qlist, staged in LDS with one coalesced read
             const int o = qoff[q];
             for (int j = lane; j < n; j += 64) list[j] = qlist[o + j];
             __builtin_amdgcn_wave_barrier();
-            merge_heads_wave<D, 0, 1>(partial_o, partial_lse, row_q, rows, q, hq, 1, Hq, list, cap, n, out_q, o_sh, lane);
+            merge_heads_wave<T, D, 0, 1>(partial_o, partial_lse, row_q, rows, q, hq, 1, Hq, list, cap, n, out_q, o_sh, lane);
         } else {  // longer than the LDS area: read in place
             const int o = qoff[q];
-            merge_heads_wave<D, 0, 1>(partial_o, partial_lse, row_q, rows, q, hq, 1, Hq, const_cast<int*>(qlist) + o, n, n, out_q, o_sh, lane);
+            merge_heads_wave<T, D, 0, 1>(partial_o, partial_lse, row_q, rows, q, hq, 1, Hq, const_cast<int*>(qlist) + o, n, n, out_q, o_sh, lane);
         }
         return;
     }
     int have = scan_rows_wave(row_q, 0, rows < cap ? rows : cap, q, list, cap, lane);
     if (rows > cap) have = -1;
     __builtin_amdgcn_wave_barrier();
-    merge_heads_wave<D, 0, 1>(partial_o, partial_lse, row_q, rows, q, hq, 1, Hq, list, cap, have, out_q, o_sh, lane);
+    merge_heads_wave<T, D, 0, 1>(partial_o, partial_lse, row_q, rows, q, hq, 1, Hq, list, cap, have, out_q, o_sh, lane);
 }
 
 // Long row lists (a long shared prefix under few queries: 64k tokens x 8 branches is 66 rows per query, and only
@@ -409,8 +449,8 @@ __global__ __launch_bounds__(256) void merge_kernel(const float* partial_o, cons
 // folding a quarter (merge_accumulate: 8 rows per round trip, so 66 rows cost 3 trips instead of 9), then one combine of the
 // four (m, L, acc) states through LDS.  Deterministic (the deal is a function of the list); its fp32 order differs from
 // merge_kernel's, so a launch uses one or the other as a function of its SHAPE only (launch_merge).
-template <int D>
-__global__ __launch_bounds__(256) void merge_coop_kernel(const float* partial_o, const float* partial_lse, int64_t rows, _Float16* out,
+template <class T, int D>
+__global__ __launch_bounds__(256) void merge_coop_kernel(const float* partial_o, const float* partial_lse, int64_t rows, e16* out,
                                                           int64_t o_st, int64_t o_sh, int cap, const int32_t* qoff,
                                                           const int32_t* qlist, const int32_t* qinl, int Hq, int hgroup) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -427,7 +467,7 @@ __global__ __launch_bounds__(256) void merge_coop_kernel(const float* partial_o,
         if (w == 0) {
             if (lane >= 1 && lane <= n) sub[lane - 1] = mine;
             __builtin_amdgcn_wave_barrier();
-            merge_heads_wave<D, 0, 1>(partial_o, partial_lse, nullptr, rows, q, hq, 1, hq + 1, sub, cap, n, out + (int64_t)q * o_st, o_sh, lane);
+            merge_heads_wave<T, D, 0, 1>(partial_o, partial_lse, nullptr, rows, q, hq, 1, hq + 1, sub, cap, n, out + (int64_t)q * o_st, o_sh, lane);
         }
         return;
     }
@@ -475,20 +515,17 @@ __global__ __launch_bounds__(256) void merge_coop_kernel(const float* partial_o,
             acc += *reinterpret_cast<const floatx4*>(xacc + i * D + 4 * lane) * f;
         }
         const float inv = L > 0.f ? 1.f / L : 0.f;
-        _Float16* dst = out + (int64_t)q * o_st + (int64_t)hq * o_sh;
-        half2v lo = {(_Float16)(acc[0] * inv), (_Float16)(acc[1] * inv)};
-        half2v hi = {(_Float16)(acc[2] * inv), (_Float16)(acc[3] * inv)};
-        *reinterpret_cast<half2v*>(dst + 4 * lane) = lo;
-        *reinterpret_cast<half2v*>(dst + 4 * lane + 2) = hi;
+        e16* dst = out + (int64_t)q * o_st + (int64_t)hq * o_sh;
+        store_row4<T>(dst + 4 * lane, acc[0] * inv, acc[1] * inv, acc[2] * inv, acc[3] * inv);
     }
 }
 
 // ---------------------------------------------------------------------------
 // paged KV append: one 16-byte piece per thread
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void kv_append_kernel(_Float16* k_base, _Float16* v_base, int64_t kv_ss, int64_t kv_sh,
-                                                         const int32_t* cache_loc, const _Float16* k_new,
-                                                         const _Float16* v_new, int64_t new_st, int n, int Hkv, int D) {
+__global__ __launch_bounds__(256) void kv_append_kernel(e16* k_base, e16* v_base, int64_t kv_ss, int64_t kv_sh,
+                                                         const int32_t* cache_loc, const e16* k_new,
+                                                         const e16* v_new, int64_t new_st, int n, int Hkv, int D) {
     const int ch_per_head = D / 8;
     const int ch_per_tok = Hkv * ch_per_head;
     const int64_t total = (int64_t)n * ch_per_tok;
@@ -551,7 +588,7 @@ static int check_launch(const char* what) {
 // is per device in HIP).
 struct DeviceState {
     int cus = 0;
-    unsigned attrs = 0;
+    uint64_t attrs = 0;  // ATTR_* bits of the fp16 instantiations, the same bits << 32 for the bf16 ones
 };
 static DeviceState& dev_state() {
     static DeviceState st[64];
@@ -572,7 +609,9 @@ static int num_cus() {
 }
 enum : unsigned { ATTR_NP = 4,  // (bits 0-1, 8-11: the head_dim 64 / 32 / 16 kernels)
                   ATTR_UNITS = 8, ATTR_NODE_UNITS = 16, ATTR_PREFILL = 32, ATTR_TREE = 64, ATTR_NP_ROPE = 128, ATTR_NP_T = 8192, ATTR_NP_ROPE_T = 16384, ATTR_NP_HD2 = 32768, ATTR_NP_HD2_T = 65536, ATTR_PREFILL_64 = 1u << 17, ATTR_NP_DYN = 1u << 18, ATTR_NP_ROPE_DYN = 1u << 19, ATTR_NP_HD2_DYN = 1u << 20 };
-static int raise_lds(const void* fn, int bytes, unsigned bit, const char* what) {  // idempotent; races are harmless
+template <class T>
+constexpr uint64_t attr_bit(unsigned bit) { return std::is_same<T, BF16>::value ? (uint64_t)bit << 32 : (uint64_t)bit; }
+static int raise_lds(const void* fn, int bytes, uint64_t bit, const char* what) {  // idempotent; races are harmless
     DeviceState& d = dev_state();
     if (d.attrs & bit) return DEFT_OK;
     const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
@@ -585,11 +624,11 @@ static int raise_lds(const void* fn, int bytes, unsigned bit, const char* what) 
 }
 
 // head_dim 16 / 32 / 64: one workgroup per (tile, KV head)
-template <int D, int MODE>
+template <class T, int D, int MODE>
 static int launch_stage1_small(const Stage1Params& p, int64_t tiles, hipStream_t stream) {
     using SM = Stage1Smem<D>;
     constexpr unsigned bit = (D == 64 ? 1u : (D == 32 ? 256u : 1024u)) << MODE;
-    int rc = raise_lds(reinterpret_cast<const void*>(&stage1_kernel<D, MODE>), SM::BYTES, bit, "stage1");
+    int rc = raise_lds(reinterpret_cast<const void*>(&stage1_kernel<T, D, MODE>), SM::BYTES, attr_bit<T>(bit), "stage1");
     if (rc) return rc;
     const int64_t grid = tiles * p.Hkv;
     if (grid <= 0) return DEFT_OK;
@@ -597,22 +636,22 @@ static int launch_stage1_small(const Stage1Params& p, int64_t tiles, hipStream_t
         set_error("stage1 grid too large: %lld", (long long)grid);
         return DEFT_EINVAL;
     }
-    hipLaunchKernelGGL((stage1_kernel<D, MODE>), dim3((unsigned)grid), dim3(256), SM::BYTES, stream, p);
+    hipLaunchKernelGGL((stage1_kernel<T, D, MODE>), dim3((unsigned)grid), dim3(256), SM::BYTES, stream, p);
     return check_launch("stage1 launch");
 }
-template <int MODE>
+template <class T, int MODE>
 static int launch_stage1_d64(int D, const Stage1Params& p, int64_t tiles, hipStream_t stream) {
-    if (D == 64) return launch_stage1_small<64, MODE>(p, tiles, stream);
-    if (D == 32) return launch_stage1_small<32, MODE>(p, tiles, stream);
-    if (D == 16) return launch_stage1_small<16, MODE>(p, tiles, stream);
+    if (D == 64) return launch_stage1_small<T, 64, MODE>(p, tiles, stream);
+    if (D == 32) return launch_stage1_small<T, 32, MODE>(p, tiles, stream);
+    if (D == 16) return launch_stage1_small<T, 16, MODE>(p, tiles, stream);
     set_error("unsupported head_dim %d", D);
     return DEFT_EUNSUPPORTED;
 }
 
 // Optional fused paged append (deft_*_decode_append_f16): this step's new K/V rows and their pool slots.
 struct AppendArgs {
-    const _Float16* k_new = nullptr;
-    const _Float16* v_new = nullptr;
+    const e16* k_new = nullptr;
+    const e16* v_new = nullptr;
     const int32_t* cache_loc = nullptr;
     int64_t new_st = 0;
     int n_new = 0;
@@ -712,6 +751,7 @@ static int launch_plan(const Stage1Params& p, int NB, const PlanView& pv, const 
 // KV heads laid out contiguously ([slot][K|V][Hkv][64], the reference's pool, memory_pool.py:61-66)
 static bool hd2_geometry(int D, int Hkv, int64_t kv_sh) { return D == 64 && Hkv % 2 == 0 && kv_sh == 64; }
 
+template <class T>
 static int launch_stage1_np(const Stage1Params& p, int64_t unit_cap, const PlanView& pv, const AppendArgs& ap,
                             hipStream_t stream, int nq, bool reread = false, bool hd2 = false) {
     using SM = NpSmem<128>;
@@ -737,15 +777,15 @@ static int launch_stage1_np(const Stage1Params& p, int64_t unit_cap, const PlanV
     // in) run the plain instantiation.
     const bool dyn = nt && p.G > 1 && (unit_cap * HP <= 16LL * num_cus() || (int64_t)nq * p.G > 160);
     int rc;
-    if (hd2) rc = dyn  ? raise_lds(reinterpret_cast<const void*>(&stage1_np_kernel<128, false, true, false, true, true>), SM::BYTES, ATTR_NP_HD2_DYN, "stage1_np_hd2_dyn")
-                 : nt ? raise_lds(reinterpret_cast<const void*>(&stage1_np_kernel<128, false, true, false, true>), SM::BYTES, ATTR_NP_HD2, "stage1_np_hd2")
-                      : raise_lds(reinterpret_cast<const void*>(&stage1_np_kernel<128, false, false, false, true>), SM::BYTES, ATTR_NP_HD2_T, "stage1_np_hd2_t");
-    else if (rope) rc = dyn  ? raise_lds(reinterpret_cast<const void*>(&stage1_np_kernel<128, true, true, true, false, true>), SM::BYTES, ATTR_NP_ROPE_DYN, "stage1_np_rope_dyn")
-                       : nt ? raise_lds(reinterpret_cast<const void*>(&stage1_np_kernel<128, true, true>), SM::BYTES, ATTR_NP_ROPE, "stage1_np_rope")
-                            : raise_lds(reinterpret_cast<const void*>(&stage1_np_kernel<128, true, false>), SM::BYTES, ATTR_NP_ROPE_T, "stage1_np_rope_t");
-    else rc = dyn  ? raise_lds(reinterpret_cast<const void*>(&stage1_np_kernel<128, false, true, false, false, true>), SM::BYTES, ATTR_NP_DYN, "stage1_np_dyn")
-             : nt ? raise_lds(reinterpret_cast<const void*>(&stage1_np_kernel<128, false, true>), SM::BYTES, ATTR_NP, "stage1_np")
-                  : raise_lds(reinterpret_cast<const void*>(&stage1_np_kernel<128, false, false>), SM::BYTES, ATTR_NP_T, "stage1_np_t");
+    if (hd2) rc = dyn  ? raise_lds(reinterpret_cast<const void*>(&stage1_np_kernel<T, 128, false, true, false, true, true>), SM::BYTES, attr_bit<T>(ATTR_NP_HD2_DYN), "stage1_np_hd2_dyn")
+                 : nt ? raise_lds(reinterpret_cast<const void*>(&stage1_np_kernel<T, 128, false, true, false, true>), SM::BYTES, attr_bit<T>(ATTR_NP_HD2), "stage1_np_hd2")
+                      : raise_lds(reinterpret_cast<const void*>(&stage1_np_kernel<T, 128, false, false, false, true>), SM::BYTES, attr_bit<T>(ATTR_NP_HD2_T), "stage1_np_hd2_t");
+    else if (rope) rc = dyn  ? raise_lds(reinterpret_cast<const void*>(&stage1_np_kernel<T, 128, true, true, true, false, true>), SM::BYTES, attr_bit<T>(ATTR_NP_ROPE_DYN), "stage1_np_rope_dyn")
+                       : nt ? raise_lds(reinterpret_cast<const void*>(&stage1_np_kernel<T, 128, true, true>), SM::BYTES, attr_bit<T>(ATTR_NP_ROPE), "stage1_np_rope")
+                            : raise_lds(reinterpret_cast<const void*>(&stage1_np_kernel<T, 128, true, false>), SM::BYTES, attr_bit<T>(ATTR_NP_ROPE_T), "stage1_np_rope_t");
+    else rc = dyn  ? raise_lds(reinterpret_cast<const void*>(&stage1_np_kernel<T, 128, false, true, false, false, true>), SM::BYTES, attr_bit<T>(ATTR_NP_DYN), "stage1_np_dyn")
+             : nt ? raise_lds(reinterpret_cast<const void*>(&stage1_np_kernel<T, 128, false, true>), SM::BYTES, attr_bit<T>(ATTR_NP), "stage1_np")
+                  : raise_lds(reinterpret_cast<const void*>(&stage1_np_kernel<T, 128, false, false>), SM::BYTES, attr_bit<T>(ATTR_NP_T), "stage1_np_t");
     if (rc) return rc;
     if (unit_cap <= 0) return DEFT_OK;
     int64_t grid = unit_cap * HP;
@@ -803,18 +843,19 @@ static int launch_stage1_np(const Stage1Params& p, int64_t unit_cap, const PlanV
     npp.dbg = g_dbg;
     npp.cos_sin = ap.cos_sin;
     const dim3 g((unsigned)grid), b(256);
-    if (hd2 && dyn) hipLaunchKernelGGL((stage1_np_kernel<128, false, true, false, true, true>), g, b, SM::BYTES, stream, npp);
-    else if (rope && dyn) hipLaunchKernelGGL((stage1_np_kernel<128, true, true, true, false, true>), g, b, SM::BYTES, stream, npp);
-    else if (dyn) hipLaunchKernelGGL((stage1_np_kernel<128, false, true, false, false, true>), g, b, SM::BYTES, stream, npp);
-    else if (hd2 && nt) hipLaunchKernelGGL((stage1_np_kernel<128, false, true, false, true>), g, b, SM::BYTES, stream, npp);
-    else if (hd2) hipLaunchKernelGGL((stage1_np_kernel<128, false, false, false, true>), g, b, SM::BYTES, stream, npp);
-    else if (rope && nt) hipLaunchKernelGGL((stage1_np_kernel<128, true, true>), g, b, SM::BYTES, stream, npp);
-    else if (rope) hipLaunchKernelGGL((stage1_np_kernel<128, true, false>), g, b, SM::BYTES, stream, npp);
-    else if (nt) hipLaunchKernelGGL((stage1_np_kernel<128, false, true>), g, b, SM::BYTES, stream, npp);
-    else hipLaunchKernelGGL((stage1_np_kernel<128, false, false>), g, b, SM::BYTES, stream, npp);
+    if (hd2 && dyn) hipLaunchKernelGGL((stage1_np_kernel<T, 128, false, true, false, true, true>), g, b, SM::BYTES, stream, npp);
+    else if (rope && dyn) hipLaunchKernelGGL((stage1_np_kernel<T, 128, true, true, true, false, true>), g, b, SM::BYTES, stream, npp);
+    else if (dyn) hipLaunchKernelGGL((stage1_np_kernel<T, 128, false, true, false, false, true>), g, b, SM::BYTES, stream, npp);
+    else if (hd2 && nt) hipLaunchKernelGGL((stage1_np_kernel<T, 128, false, true, false, true>), g, b, SM::BYTES, stream, npp);
+    else if (hd2) hipLaunchKernelGGL((stage1_np_kernel<T, 128, false, false, false, true>), g, b, SM::BYTES, stream, npp);
+    else if (rope && nt) hipLaunchKernelGGL((stage1_np_kernel<T, 128, true, true>), g, b, SM::BYTES, stream, npp);
+    else if (rope) hipLaunchKernelGGL((stage1_np_kernel<T, 128, true, false>), g, b, SM::BYTES, stream, npp);
+    else if (nt) hipLaunchKernelGGL((stage1_np_kernel<T, 128, false, true>), g, b, SM::BYTES, stream, npp);
+    else hipLaunchKernelGGL((stage1_np_kernel<T, 128, false, false>), g, b, SM::BYTES, stream, npp);
     return check_launch("stage1 np launch");
 }
 
+template <class T>
 static int launch_merge(int D, const Workspace& ws, const PlanView* pv, const int32_t* row_q, int64_t rows, void* out,
                         int64_t o_st, int64_t o_sh, int nq, int Hq, int hgroup, hipStream_t stream) {
     if (nq <= 0) return DEFT_OK;
@@ -837,13 +878,13 @@ static int launch_merge(int D, const Workspace& ws, const PlanView* pv, const in
     if (D == 128 && lists && nq <= 16 && (int64_t)nq * Hq <= 1024) {
         const int ccap = (int)std::min<int64_t>(std::max<int64_t>(rows / 4 + 2, 16), MERGE_LIST_CAP);  // (>= 8: the single-wave path stages up to 8 rows)
         const size_t clds = sizeof(int) * 4 * (size_t)ccap + sizeof(float) * (4 * 128 + 8);
-        hipLaunchKernelGGL((merge_coop_kernel<128>), dim3((unsigned)Hq, (unsigned)nq), dim3(256), clds, stream, ws.partial_o,
-                           ws.partial_lse, rows, static_cast<_Float16*>(out), o_st, o_sh, ccap, qoff, qlist, qinl, Hq, hgroup);
+        hipLaunchKernelGGL((merge_coop_kernel<T, 128>), dim3((unsigned)Hq, (unsigned)nq), dim3(256), clds, stream, ws.partial_o,
+                           ws.partial_lse, rows, static_cast<e16*>(out), o_st, o_sh, ccap, qoff, qlist, qinl, Hq, hgroup);
         return check_launch("merge (cooperative) launch");
     }
 #define DEFT_MERGE_LAUNCH(DD)                                                                                              \
-    hipLaunchKernelGGL((merge_kernel<DD>), grid, dim3(256), lds, stream, ws.partial_o, ws.partial_lse, row_q, rows,         \
-                       static_cast<_Float16*>(out), o_st, o_sh, Hq, cap, lists, qoff, qlist, qinl, nq, hgroup)
+    hipLaunchKernelGGL((merge_kernel<T, DD>), grid, dim3(256), lds, stream, ws.partial_o, ws.partial_lse, row_q, rows,         \
+                       static_cast<e16*>(out), o_st, o_sh, Hq, cap, lists, qoff, qlist, qinl, nq, hgroup)
     if (D == 128) DEFT_MERGE_LAUNCH(128);
     else if (D == 64) DEFT_MERGE_LAUNCH(64);
     else if (D == 32) DEFT_MERGE_LAUNCH(32);
@@ -991,8 +1032,16 @@ static int fill_rope(AppendArgs& ap, const float* cos_sin_rows, int rotary_dim, 
     return DEFT_OK;
 }
 
+}  // extern "C"
+
+// Paged append behind both deft_kv_append_* entry points and in front of the tile-per-workgroup stage 1: one launch for either
+// element type -- the copy moves 16-byte pieces and never looks inside them.
+static int kv_append_impl(void* k_base, void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head, const int32_t* cache_loc,
+                          const void* k_new, const void* v_new, int64_t new_stride_tok, int n, int Hkv, int D, void* stream);
+
 // Shared body of the Flatten entry points: stage 1 into the workspace; reports which
 // partial-row -> query map the merge must read.
+template <class T>
 static int flatten_stage1_impl(const void* q, int64_t q_stride_tok, int64_t q_stride_head, const void* k_base,
                                const void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head, const int64_t* block_q,
                                const int64_t* block_q_cnts, const int64_t* block_q_offset, const int64_t* block_bitmasks,
@@ -1017,11 +1066,11 @@ static int flatten_stage1_impl(const void* q, int64_t q_stride_tok, int64_t q_st
         return DEFT_EWORKSPACE;
     }
     Stage1Params p{};
-    p.q = static_cast<const _Float16*>(q);
+    p.q = static_cast<const e16*>(q);
     p.q_st = q_stride_tok;
     p.q_sh = q_stride_head;
-    p.k = static_cast<const _Float16*>(k_base);
-    p.v = static_cast<const _Float16*>(v_base);
+    p.k = static_cast<const e16*>(k_base);
+    p.v = static_cast<const e16*>(v_base);
     p.kv_ss = kv_stride_slot;
     p.kv_sh = kv_stride_head;
     p.block_q = block_q;
@@ -1051,16 +1100,18 @@ static int flatten_stage1_impl(const void* q, int64_t q_stride_tok, int64_t q_st
         }
         *row_q_out = pv.row_q;
         *pv_out = pv;
-        return launch_stage1_np(p, cap, pv, ap, st, nq, false, hd2);
+        return launch_stage1_np<T>(p, cap, pv, ap, st, nq, false, hd2);
     }
     if (ap.k_new) {  // head_dim 64 (tile-per-workgroup form): separate append launch first
-        rc = deft_kv_append_f16(const_cast<void*>(k_base), const_cast<void*>(v_base), kv_stride_slot, kv_stride_head,
+        rc = kv_append_impl(const_cast<void*>(k_base), const_cast<void*>(v_base), kv_stride_slot, kv_stride_head,
                                 ap.cache_loc, ap.k_new, ap.v_new, ap.new_st, ap.n_new, Hkv, D, stream);
         if (rc) return rc;
     }
     *row_q_out = ws.row_q;
-    return launch_stage1_d64<0>(D, p, NB, st);
+    return launch_stage1_d64<T, 0>(D, p, NB, st);
 }
+
+extern "C" {
 
 size_t deft_flatten_plan_bytes(int NB, int P, int Hq, int Hkv) {
     if (Hq <= 0 || Hkv <= 0 || Hq % Hkv) return 0;
@@ -1141,7 +1192,10 @@ int deft_flatten_build_plan_dims(const int64_t* block_q, const int64_t* block_q_
     return launch_plan(p, NB, pv, ap, static_cast<hipStream_t>(stream), dims);
 }
 
-int deft_flatten_stage1_f16(const void* q, int64_t q_stride_tok, int64_t q_stride_head, const void* k_base,
+}  // extern "C"
+
+template <class T>
+static int flatten_stage1_t(const void* q, int64_t q_stride_tok, int64_t q_stride_head, const void* k_base,
                             const void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head, const int64_t* block_q,
                             const int64_t* block_q_cnts, const int64_t* block_q_offset, const int64_t* block_bitmasks,
                             const int64_t* block_kv, const int64_t* block_lens, int NB, int P, int nq, int Hq, int Hkv,
@@ -1153,11 +1207,12 @@ int deft_flatten_stage1_f16(const void* q, int64_t q_stride_tok, int64_t q_strid
     Workspace ws;
     const int32_t* row_q = nullptr;
     PlanView pv;
-    return flatten_stage1_impl(q, q_stride_tok, q_stride_head, k_base, v_base, kv_stride_slot, kv_stride_head, block_q,
+    return flatten_stage1_impl<T>(q, q_stride_tok, q_stride_head, k_base, v_base, kv_stride_slot, kv_stride_head, block_q,
                                block_q_cnts, block_q_offset, block_bitmasks, block_kv, block_lens, NB, P, nq, Hq, Hkv, D,
                                scale, plan, workspace, workspace_bytes, stream, AppendArgs(), &ws, &row_q, &pv);
 }
 
+template <class T>
 static int flatten_decode_impl(const void* q, int64_t q_stride_tok, int64_t q_stride_head, const void* k_base,
                                const void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head, void* out,
                                int64_t o_stride_tok, int64_t o_stride_head, const int64_t* block_q,
@@ -1177,27 +1232,29 @@ static int flatten_decode_impl(const void* q, int64_t q_stride_tok, int64_t q_st
     Workspace ws;
     const int32_t* row_q = nullptr;
     PlanView pv;
-    rc = flatten_stage1_impl(q, q_stride_tok, q_stride_head, k_base, v_base, kv_stride_slot, kv_stride_head, block_q,
+    rc = flatten_stage1_impl<T>(q, q_stride_tok, q_stride_head, k_base, v_base, kv_stride_slot, kv_stride_head, block_q,
                              block_q_cnts, block_q_offset, block_bitmasks, block_kv, block_lens, NB, P, nq, Hq, Hkv, D, scale,
                              plan, workspace, workspace_bytes, stream, ap, &ws, &row_q, &pv);
     if (rc) return rc;
-    return launch_merge(D, ws, pv.hdr ? &pv : nullptr, row_q, P, out, o_stride_tok, o_stride_head, nq, Hq,
+    return launch_merge<T>(D, ws, pv.hdr ? &pv : nullptr, row_q, P, out, o_stride_tok, o_stride_head, nq, Hq,
                         (Hq / Hkv) * (hd2_geometry(D, Hkv, kv_stride_head) && !ap.cos_sin ? 2 : 1), static_cast<hipStream_t>(stream));
 }
 
-int deft_flatten_decode_f16(const void* q, int64_t q_stride_tok, int64_t q_stride_head, const void* k_base,
+template <class T>
+static int flatten_decode_t(const void* q, int64_t q_stride_tok, int64_t q_stride_head, const void* k_base,
                             const void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head, void* out,
                             int64_t o_stride_tok, int64_t o_stride_head, const int64_t* block_q,
                             const int64_t* block_q_cnts, const int64_t* block_q_offset, const int64_t* block_bitmasks,
                             const int64_t* block_kv, const int64_t* block_lens, int NB, int P, int nq, int Hq, int Hkv,
                             int D, float scale, const void* plan, void* workspace, size_t workspace_bytes, void* stream) {
-    return flatten_decode_impl(q, q_stride_tok, q_stride_head, k_base, v_base, kv_stride_slot, kv_stride_head, out,
+    return flatten_decode_impl<T>(q, q_stride_tok, q_stride_head, k_base, v_base, kv_stride_slot, kv_stride_head, out,
                                o_stride_tok, o_stride_head, block_q, block_q_cnts, block_q_offset, block_bitmasks, block_kv,
                                block_lens, NB, P, nq, Hq, Hkv, D, scale, plan, workspace, workspace_bytes, stream,
                                AppendArgs());
 }
 
-int deft_flatten_decode_append_f16(const void* q, int64_t q_stride_tok, int64_t q_stride_head, void* k_base, void* v_base,
+template <class T>
+static int flatten_decode_append_t(const void* q, int64_t q_stride_tok, int64_t q_stride_head, void* k_base, void* v_base,
                                    int64_t kv_stride_slot, int64_t kv_stride_head, void* out, int64_t o_stride_tok,
                                    int64_t o_stride_head, const int64_t* block_q, const int64_t* block_q_cnts,
                                    const int64_t* block_q_offset, const int64_t* block_bitmasks, const int64_t* block_kv,
@@ -1205,8 +1262,8 @@ int deft_flatten_decode_append_f16(const void* q, int64_t q_stride_tok, int64_t 
                                    const int32_t* cache_loc, const void* k_new, const void* v_new, int64_t new_stride_tok,
                                    int n_new, const void* plan, void* workspace, size_t workspace_bytes, void* stream) {
     AppendArgs ap;
-    ap.k_new = static_cast<const _Float16*>(k_new);
-    ap.v_new = static_cast<const _Float16*>(v_new);
+    ap.k_new = static_cast<const e16*>(k_new);
+    ap.v_new = static_cast<const e16*>(v_new);
     ap.cache_loc = cache_loc;
     ap.new_st = new_stride_tok;
     ap.n_new = n_new;
@@ -1214,12 +1271,13 @@ int deft_flatten_decode_append_f16(const void* q, int64_t q_stride_tok, int64_t 
         set_error("fused append needs k_new, v_new and cache_loc");
         return DEFT_EINVAL;
     }
-    return flatten_decode_impl(q, q_stride_tok, q_stride_head, k_base, v_base, kv_stride_slot, kv_stride_head, out,
+    return flatten_decode_impl<T>(q, q_stride_tok, q_stride_head, k_base, v_base, kv_stride_slot, kv_stride_head, out,
                                o_stride_tok, o_stride_head, block_q, block_q_cnts, block_q_offset, block_bitmasks, block_kv,
                                block_lens, NB, P, nq, Hq, Hkv, D, scale, plan, workspace, workspace_bytes, stream, ap);
 }
 
-int deft_flatten_decode_rope_append_f16(const void* q, int64_t q_stride_tok, int64_t q_stride_head, void* k_base, void* v_base,
+template <class T>
+static int flatten_decode_rope_append_t(const void* q, int64_t q_stride_tok, int64_t q_stride_head, void* k_base, void* v_base,
                                         int64_t kv_stride_slot, int64_t kv_stride_head, void* out, int64_t o_stride_tok,
                                         int64_t o_stride_head, const int64_t* block_q, const int64_t* block_q_cnts,
                                         const int64_t* block_q_offset, const int64_t* block_bitmasks, const int64_t* block_kv,
@@ -1228,8 +1286,8 @@ int deft_flatten_decode_rope_append_f16(const void* q, int64_t q_stride_tok, int
                                         int n_new, const float* cos_sin_rows, int rotary_dim, int is_neox_style,
                                         const void* plan, void* workspace, size_t workspace_bytes, void* stream) {
     AppendArgs ap;
-    ap.k_new = static_cast<const _Float16*>(k_new);
-    ap.v_new = static_cast<const _Float16*>(v_new);
+    ap.k_new = static_cast<const e16*>(k_new);
+    ap.v_new = static_cast<const e16*>(v_new);
     ap.cache_loc = cache_loc;
     ap.new_st = new_stride_tok;
     ap.n_new = n_new;
@@ -1239,10 +1297,12 @@ int deft_flatten_decode_rope_append_f16(const void* q, int64_t q_stride_tok, int
     }
     const int rc = fill_rope(ap, cos_sin_rows, rotary_dim, is_neox_style, q_stride_tok, q_stride_head, Hq, D);
     if (rc) return rc;
-    return flatten_decode_impl(q, q_stride_tok, q_stride_head, k_base, v_base, kv_stride_slot, kv_stride_head, out,
+    return flatten_decode_impl<T>(q, q_stride_tok, q_stride_head, k_base, v_base, kv_stride_slot, kv_stride_head, out,
                                o_stride_tok, o_stride_head, block_q, block_q_cnts, block_q_offset, block_bitmasks, block_kv,
                                block_lens, NB, P, nq, Hq, Hkv, D, scale, plan, workspace, workspace_bytes, stream, ap);
 }
+
+extern "C" {
 
 static int launch_node_plan(const Stage1Params& p, int NE, int64_t rows_cap, const PlanView& pv, const AppendArgs& ap,
                             hipStream_t stream, int keep_err = 0, const int32_t* dims = nullptr, int win_tiles = 0,
@@ -1352,8 +1412,10 @@ int deft_node_build_plan_dims(const int64_t* node_kv, const int64_t* node_kv_off
                                 stream);
 }
 
+
 }  // extern "C"
 
+template <class T>
 static int node_decode_impl(const void* q, int64_t q_stride_tok, int64_t q_stride_head, const void* k_base,
                             const void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head, void* out,
                             int64_t o_stride_tok, int64_t o_stride_head, const int64_t* node_kv,
@@ -1385,11 +1447,11 @@ static int node_decode_impl(const void* q, int64_t q_stride_tok, int64_t q_strid
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
     Stage1Params p{};
-    p.q = static_cast<const _Float16*>(q);
+    p.q = static_cast<const e16*>(q);
     p.q_st = q_stride_tok;
     p.q_sh = q_stride_head;
-    p.k = static_cast<const _Float16*>(k_base);
-    p.v = static_cast<const _Float16*>(v_base);
+    p.k = static_cast<const e16*>(k_base);
+    p.v = static_cast<const e16*>(v_base);
     p.kv_ss = kv_stride_slot;
     p.kv_sh = kv_stride_head;
     p.node_kv = node_kv;
@@ -1415,13 +1477,13 @@ static int node_decode_impl(const void* q, int64_t q_stride_tok, int64_t q_strid
             rc = launch_node_plan(p, NE, rows, pv, ap, st);
             if (rc) return rc;
         }
-        rc = launch_stage1_np(p, tiles * G, pv, ap, st, nq, /*reread=*/rows_per_tile == 1, hd2);
+        rc = launch_stage1_np<T>(p, tiles * G, pv, ap, st, nq, /*reread=*/rows_per_tile == 1, hd2);
         if (rc) return rc;
-        return launch_merge(D, ws, &pv, pv.row_q, rows, out, o_stride_tok, o_stride_head, nq, Hq, G * (hd2 ? 2 : 1), st);
+        return launch_merge<T>(D, ws, &pv, pv.row_q, rows, out, o_stride_tok, o_stride_head, nq, Hq, G * (hd2 ? 2 : 1), st);
     }
     // tile-per-workgroup form (head_dim 64)
     if (ap.k_new) {  // separate append launch first
-        rc = deft_kv_append_f16(const_cast<void*>(k_base), const_cast<void*>(v_base), kv_stride_slot, kv_stride_head,
+        rc = kv_append_impl(const_cast<void*>(k_base), const_cast<void*>(v_base), kv_stride_slot, kv_stride_head,
                                 ap.cache_loc, ap.k_new, ap.v_new, ap.new_st, ap.n_new, Hkv, D, stream);
         if (rc) return rc;
     }
@@ -1435,27 +1497,28 @@ static int node_decode_impl(const void* q, int64_t q_stride_tok, int64_t q_strid
     rc = check_launch("node prep launch");
     if (rc) return rc;
     p.desc = ws.desc;
-    rc = launch_stage1_d64<1>(D, p, tiles, st);
+    rc = launch_stage1_d64<T, 1>(D, p, tiles, st);
     if (rc) return rc;
-    return launch_merge(D, ws, nullptr, ws.row_q, rows, out, o_stride_tok, o_stride_head, nq, Hq, 1, st);
+    return launch_merge<T>(D, ws, nullptr, ws.row_q, rows, out, o_stride_tok, o_stride_head, nq, Hq, 1, st);
 }
 
-extern "C" {
 
-int deft_node_decode_f16(const void* q, int64_t q_stride_tok, int64_t q_stride_head, const void* k_base,
+template <class T>
+static int node_decode_t(const void* q, int64_t q_stride_tok, int64_t q_stride_head, const void* k_base,
                          const void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head, void* out,
                          int64_t o_stride_tok, int64_t o_stride_head, const int64_t* node_kv,
                          const int64_t* node_kv_offset, const int64_t* node_kv_len, const int64_t* node_q,
                          const int64_t* node_q_offset, const int64_t* node_q_len, int NE, int P, int64_t total_kv, int nq,
                          int Hq, int Hkv, int D, float scale, const void* plan, void* workspace, size_t workspace_bytes,
                          void* stream) {
-    return node_decode_impl(q, q_stride_tok, q_stride_head, k_base, v_base, kv_stride_slot, kv_stride_head, out,
+    return node_decode_impl<T>(q, q_stride_tok, q_stride_head, k_base, v_base, kv_stride_slot, kv_stride_head, out,
                             o_stride_tok, o_stride_head, node_kv, node_kv_offset, node_kv_len, node_q, node_q_offset,
                             node_q_len, NE, P, total_kv, nq, Hq, Hkv, D, scale, plan, workspace, workspace_bytes, stream,
                             AppendArgs());
 }
 
-int deft_node_decode_append_f16(const void* q, int64_t q_stride_tok, int64_t q_stride_head, void* k_base, void* v_base,
+template <class T>
+static int node_decode_append_t(const void* q, int64_t q_stride_tok, int64_t q_stride_head, void* k_base, void* v_base,
                                 int64_t kv_stride_slot, int64_t kv_stride_head, void* out, int64_t o_stride_tok,
                                 int64_t o_stride_head, const int64_t* node_kv, const int64_t* node_kv_offset,
                                 const int64_t* node_kv_len, const int64_t* node_q, const int64_t* node_q_offset,
@@ -1464,8 +1527,8 @@ int deft_node_decode_append_f16(const void* q, int64_t q_stride_tok, int64_t q_s
                                 int64_t new_stride_tok, int n_new, const void* plan, void* workspace,
                                 size_t workspace_bytes, void* stream) {
     AppendArgs ap;
-    ap.k_new = static_cast<const _Float16*>(k_new);
-    ap.v_new = static_cast<const _Float16*>(v_new);
+    ap.k_new = static_cast<const e16*>(k_new);
+    ap.v_new = static_cast<const e16*>(v_new);
     ap.cache_loc = cache_loc;
     ap.new_st = new_stride_tok;
     ap.n_new = n_new;
@@ -1473,12 +1536,13 @@ int deft_node_decode_append_f16(const void* q, int64_t q_stride_tok, int64_t q_s
         set_error("fused append needs k_new, v_new and cache_loc");
         return DEFT_EINVAL;
     }
-    return node_decode_impl(q, q_stride_tok, q_stride_head, k_base, v_base, kv_stride_slot, kv_stride_head, out,
+    return node_decode_impl<T>(q, q_stride_tok, q_stride_head, k_base, v_base, kv_stride_slot, kv_stride_head, out,
                             o_stride_tok, o_stride_head, node_kv, node_kv_offset, node_kv_len, node_q, node_q_offset,
                             node_q_len, NE, P, total_kv, nq, Hq, Hkv, D, scale, plan, workspace, workspace_bytes, stream, ap);
 }
 
-int deft_node_decode_rope_append_f16(const void* q, int64_t q_stride_tok, int64_t q_stride_head, void* k_base, void* v_base,
+template <class T>
+static int node_decode_rope_append_t(const void* q, int64_t q_stride_tok, int64_t q_stride_head, void* k_base, void* v_base,
                                      int64_t kv_stride_slot, int64_t kv_stride_head, void* out, int64_t o_stride_tok,
                                      int64_t o_stride_head, const int64_t* node_kv, const int64_t* node_kv_offset,
                                      const int64_t* node_kv_len, const int64_t* node_q, const int64_t* node_q_offset,
@@ -1488,8 +1552,8 @@ int deft_node_decode_rope_append_f16(const void* q, int64_t q_stride_tok, int64_
                                      int is_neox_style, const void* plan, void* workspace, size_t workspace_bytes,
                                      void* stream) {
     AppendArgs ap;
-    ap.k_new = static_cast<const _Float16*>(k_new);
-    ap.v_new = static_cast<const _Float16*>(v_new);
+    ap.k_new = static_cast<const e16*>(k_new);
+    ap.v_new = static_cast<const e16*>(v_new);
     ap.cache_loc = cache_loc;
     ap.new_st = new_stride_tok;
     ap.n_new = n_new;
@@ -1499,14 +1563,14 @@ int deft_node_decode_rope_append_f16(const void* q, int64_t q_stride_tok, int64_
     }
     const int rc = fill_rope(ap, cos_sin_rows, rotary_dim, is_neox_style, q_stride_tok, q_stride_head, Hq, D);
     if (rc) return rc;
-    return node_decode_impl(q, q_stride_tok, q_stride_head, k_base, v_base, kv_stride_slot, kv_stride_head, out,
+    return node_decode_impl<T>(q, q_stride_tok, q_stride_head, k_base, v_base, kv_stride_slot, kv_stride_head, out,
                             o_stride_tok, o_stride_head, node_kv, node_kv_offset, node_kv_len, node_q, node_q_offset,
                             node_q_len, NE, P, total_kv, nq, Hq, Hkv, D, scale, plan, workspace, workspace_bytes, stream, ap);
 }
 
-int deft_kv_append_f16(void* k_base, void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head,
-                       const int32_t* cache_loc, const void* k_new, const void* v_new, int64_t new_stride_tok, int n,
-                       int Hkv, int D, void* stream) {
+static int kv_append_impl(void* k_base, void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head,
+                          const int32_t* cache_loc, const void* k_new, const void* v_new, int64_t new_stride_tok, int n,
+                          int Hkv, int D, void* stream) {
     if (n == 0) return DEFT_OK;
     if (!k_base || !v_base || !cache_loc || !k_new || !v_new || n < 0 || Hkv <= 0 || D <= 0 || (D % 8)) {
         set_error("bad kv_append arguments (n=%d Hkv=%d D=%d)", n, Hkv, D);
@@ -1521,13 +1585,13 @@ int deft_kv_append_f16(void* k_base, void* v_base, int64_t kv_stride_slot, int64
     const int64_t blocks = (total + 255) / 256;
     const unsigned grid = (unsigned)(blocks < 2048 ? blocks : 2048);
     hipLaunchKernelGGL(kv_append_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       static_cast<_Float16*>(k_base), static_cast<_Float16*>(v_base), kv_stride_slot, kv_stride_head,
-                       cache_loc, static_cast<const _Float16*>(k_new), static_cast<const _Float16*>(v_new),
+                       static_cast<e16*>(k_base), static_cast<e16*>(v_base), kv_stride_slot, kv_stride_head,
+                       cache_loc, static_cast<const e16*>(k_new), static_cast<const e16*>(v_new),
                        new_stride_tok, n, Hkv, D);
     return check_launch("kv_append launch");
 }
 
-int deft_flatten_read_partials(const void* workspace, size_t workspace_bytes, int NB, int P, int nq, int Hq, int Hkv, int D,
+extern "C" int deft_flatten_read_partials(const void* workspace, size_t workspace_bytes, int NB, int P, int nq, int Hq, int Hkv, int D,
                                float* partial_o_dev, float* partial_lse_dev, void* stream) {
     (void)nq;
     (void)Hkv;
@@ -1551,7 +1615,6 @@ int deft_flatten_read_partials(const void* workspace, size_t workspace_bytes, in
     return DEFT_OK;
 }
 
-}  // extern "C"
 
 
 // ---------------------------------------------------------------------------
@@ -1623,6 +1686,7 @@ static SeqPlan seq_plan_view(void* base, int nq, int64_t total, int Hq, int Hkv)
 
 }  // namespace deft
 
+
 extern "C" {
 
 size_t deft_seq_plan_bytes(int nq, int64_t total_tokens, int Hq, int Hkv) {
@@ -1687,6 +1751,9 @@ int deft_seq_build_plan(const int32_t* req_to_token, int64_t req_stride, const i
     return launch_node_plan(p, nq, tiles, pv, ap, st, 1);
 }
 
+}  // extern "C"
+
+template <class T>
 static int seq_decode_impl(const void* q, int64_t q_stride_tok, int64_t q_stride_head, const void* k_base,
                            const void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head, void* out,
                            int64_t o_stride_tok, int64_t o_stride_head, const void* plan, int nq, int64_t total_tokens,
@@ -1697,22 +1764,24 @@ static int seq_decode_impl(const void* q, int64_t q_stride_tok, int64_t q_stride
         return DEFT_EINVAL;
     }
     const SeqPlan sp = seq_plan_view(const_cast<void*>(plan), nq, total_tokens, Hq, Hkv);
-    return node_decode_impl(q, q_stride_tok, q_stride_head, k_base, v_base, kv_stride_slot, kv_stride_head, out,
+    return node_decode_impl<T>(q, q_stride_tok, q_stride_head, k_base, v_base, kv_stride_slot, kv_stride_head, out,
                             o_stride_tok, o_stride_head, sp.node_kv, sp.node_kv_offset, sp.node_kv_len, sp.node_q,
                             sp.node_q_offset, sp.node_q_len, nq, nq, total_tokens, nq, Hq, Hkv, D, scale,
                             D == 128 ? sp.node_plan : nullptr, workspace, workspace_bytes, stream, ap, 1);
 }
 
-int deft_seq_decode_f16(const void* q, int64_t q_stride_tok, int64_t q_stride_head, const void* k_base, const void* v_base,
+template <class T>
+static int seq_decode_t(const void* q, int64_t q_stride_tok, int64_t q_stride_head, const void* k_base, const void* v_base,
                         int64_t kv_stride_slot, int64_t kv_stride_head, void* out, int64_t o_stride_tok,
                         int64_t o_stride_head, const void* plan, int nq, int64_t total_tokens, int Hq, int Hkv, int D,
                         float scale, void* workspace, size_t workspace_bytes, void* stream) {
-    return seq_decode_impl(q, q_stride_tok, q_stride_head, k_base, v_base, kv_stride_slot, kv_stride_head, out,
+    return seq_decode_impl<T>(q, q_stride_tok, q_stride_head, k_base, v_base, kv_stride_slot, kv_stride_head, out,
                            o_stride_tok, o_stride_head, plan, nq, total_tokens, Hq, Hkv, D, scale, workspace,
                            workspace_bytes, stream, AppendArgs());
 }
 
-int deft_seq_decode_append_f16(const void* q, int64_t q_stride_tok, int64_t q_stride_head, void* k_base, void* v_base,
+template <class T>
+static int seq_decode_append_t(const void* q, int64_t q_stride_tok, int64_t q_stride_head, void* k_base, void* v_base,
                                int64_t kv_stride_slot, int64_t kv_stride_head, void* out, int64_t o_stride_tok,
                                int64_t o_stride_head, const void* plan, int nq, int64_t total_tokens, int Hq, int Hkv,
                                int D, float scale, const int32_t* cache_loc, const void* k_new, const void* v_new,
@@ -1722,17 +1791,16 @@ int deft_seq_decode_append_f16(const void* q, int64_t q_stride_tok, int64_t q_st
         return DEFT_EINVAL;
     }
     AppendArgs ap;
-    ap.k_new = static_cast<const _Float16*>(k_new);
-    ap.v_new = static_cast<const _Float16*>(v_new);
+    ap.k_new = static_cast<const e16*>(k_new);
+    ap.v_new = static_cast<const e16*>(v_new);
     ap.cache_loc = cache_loc;
     ap.new_st = new_stride_tok;
     ap.n_new = n_new;
-    return seq_decode_impl(q, q_stride_tok, q_stride_head, k_base, v_base, kv_stride_slot, kv_stride_head, out,
+    return seq_decode_impl<T>(q, q_stride_tok, q_stride_head, k_base, v_base, kv_stride_slot, kv_stride_head, out,
                            o_stride_tok, o_stride_head, plan, nq, total_tokens, Hq, Hkv, D, scale, workspace,
                            workspace_bytes, stream, ap);
 }
 
-}  // extern "C"
 
 
 // ---------------------------------------------------------------------------
@@ -1740,12 +1808,13 @@ int deft_seq_decode_append_f16(const void* q, int64_t q_stride_tok, int64_t q_st
 // (LlamaAttention.forward, DeFT/deft/models/llama2.py:108-110 -> RotaryEmbedding.forward_cuda,
 // DeFT/deft/layers/rotary_embedding.py:157-177, which calls flashinfer.rope.apply_rope_with_cos_sin_cache_inplace:
 // NeoX pairing (d, d + rot/2), cos|sin cache in fp32 (llama2.py:86-93 passes dtype=float32), arithmetic in fp32,
-// one rounding back to fp16).  flashinfer is not part of the reference tree; its published algorithm is restated
+// one rounding back to the element type).  flashinfer is not part of the reference tree; its published algorithm is restated
 // in oracle/rope.py.  No FMA contraction, so the fp32 products and sums are the oracle's.
 // ---------------------------------------------------------------------------
 namespace deft {
 
-__global__ __launch_bounds__(256) void rope_qk_kernel(_Float16* q, int64_t q_st, int64_t q_sh, int Hq, _Float16* k,
+template <class T>
+__global__ __launch_bounds__(256) void rope_qk_kernel(e16* q, int64_t q_st, int64_t q_sh, int Hq, e16* k,
                                                        int64_t k_st, int64_t k_sh, int Hk, const int64_t* positions,
                                                        const float* cos_sin, int64_t cache_stride, int n, int D, int rot,
                                                        int neox) {
@@ -1758,23 +1827,25 @@ __global__ __launch_bounds__(256) void rope_qk_kernel(_Float16* q, int64_t q_st,
         const int rem = (int)(i - (int64_t)tok * per_tok);
         const int hd = rem / half;
         const int j = rem - hd * half;
-        _Float16* row = hd < Hq ? q + (int64_t)tok * q_st + (int64_t)hd * q_sh : k + (int64_t)tok * k_st + (int64_t)(hd - Hq) * k_sh;
+        typename T::scalar* row =
+            reinterpret_cast<typename T::scalar*>(hd < Hq ? q + (int64_t)tok * q_st + (int64_t)hd * q_sh : k + (int64_t)tok * k_st + (int64_t)(hd - Hq) * k_sh);
         const float* cs = cos_sin + positions[tok] * cache_stride;
         const float c = cs[j], sn = cs[half + j];
         const int i1 = neox ? j : 2 * j, i2 = neox ? j + half : 2 * j + 1;
-        const float x1 = (float)row[i1], x2 = (float)row[i2];
+        const float x1 = T::to_float(row[i1]), x2 = T::to_float(row[i2]);
         const float o1 = x1 * c - x2 * sn;
         const float o2 = x2 * c + x1 * sn;
-        row[i1] = (_Float16)o1;
-        row[i2] = (_Float16)o2;
+        row[i1] = T::from_float(o1);
+        row[i2] = T::from_float(o2);
     }
 }
 
 }  // namespace deft
 
-extern "C" int deft_rope_qk_f16(void* q, int64_t q_stride_tok, int64_t q_stride_head, int Hq, void* k, int64_t k_stride_tok,
-                                int64_t k_stride_head, int Hk, const int64_t* positions, const float* cos_sin_cache,
-                                int64_t cache_stride, int n, int D, int rotary_dim, int is_neox_style, void* stream) {
+template <class T>
+static int rope_qk_t(void* q, int64_t q_stride_tok, int64_t q_stride_head, int Hq, void* k, int64_t k_stride_tok,
+                     int64_t k_stride_head, int Hk, const int64_t* positions, const float* cos_sin_cache,
+                     int64_t cache_stride, int n, int D, int rotary_dim, int is_neox_style, void* stream) {
     if (n == 0) return DEFT_OK;
     if (!q || !k || !positions || !cos_sin_cache || n < 0 || Hq <= 0 || Hk < 0 || D <= 0 || rotary_dim <= 0 ||
         rotary_dim > D || (rotary_dim & 1) || cache_stride < rotary_dim) {
@@ -1783,9 +1854,9 @@ extern "C" int deft_rope_qk_f16(void* q, int64_t q_stride_tok, int64_t q_stride_
     }
     const int64_t total = (int64_t)n * (Hq + Hk) * (rotary_dim / 2);
     const int64_t blocks = (total + 255) / 256;
-    hipLaunchKernelGGL(deft::rope_qk_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), static_cast<_Float16*>(q), q_stride_tok, q_stride_head, Hq,
-                       static_cast<_Float16*>(k), k_stride_tok, k_stride_head, Hk, positions, cos_sin_cache, cache_stride, n,
+    hipLaunchKernelGGL(deft::rope_qk_kernel<T>, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), static_cast<e16*>(q), q_stride_tok, q_stride_head, Hq,
+                       static_cast<e16*>(k), k_stride_tok, k_stride_head, Hk, positions, cos_sin_cache, cache_stride, n,
                        D, rotary_dim, is_neox_style ? 1 : 0);
     return deft::check_launch("rope launch");
 }
@@ -1819,11 +1890,12 @@ extern "C" int deft_rope_gather_rows(const int64_t* positions, const float* cos_
 // Causal prefill attention (prefill.h): context_attention_fwd
 // (DeFT/deft/layers/attention/context_flashattention_nopad.py:130-195)
 // ---------------------------------------------------------------------------
-extern "C" int deft_prefill_f16(const void* q, int64_t q_stride_tok, int64_t q_stride_head, const void* k,
-                                int64_t k_stride_tok, int64_t k_stride_head, const void* v, int64_t v_stride_tok,
-                                int64_t v_stride_head, void* out, int64_t o_stride_tok, int64_t o_stride_head,
-                                const int32_t* b_start_loc, const int32_t* b_seq_len, int batch, int max_input_len, int Hq,
-                                int Hkv, int D, float scale, void* stream) {
+template <class T>
+static int prefill_t(const void* q, int64_t q_stride_tok, int64_t q_stride_head, const void* k,
+                     int64_t k_stride_tok, int64_t k_stride_head, const void* v, int64_t v_stride_tok,
+                     int64_t v_stride_head, void* out, int64_t o_stride_tok, int64_t o_stride_head,
+                     const int32_t* b_start_loc, const int32_t* b_seq_len, int batch, int max_input_len, int Hq,
+                     int Hkv, int D, float scale, void* stream) {
     using namespace deft;
     if (batch == 0 || max_input_len == 0) return DEFT_OK;
     if (!q || !k || !v || !out || !b_start_loc || !b_seq_len || batch < 0 || max_input_len < 0 || Hq <= 0 || Hkv <= 0 ||
@@ -1842,17 +1914,17 @@ extern "C" int deft_prefill_f16(const void* q, int64_t q_stride_tok, int64_t q_s
         return DEFT_EINVAL;
     }
     if (D == 128) {
-        const int rc = raise_lds(reinterpret_cast<const void*>(&prefill_kernel<128>), PrefillSmem<128>::BYTES, ATTR_PREFILL, "prefill");
+        const int rc = raise_lds(reinterpret_cast<const void*>(&prefill_kernel<T, 128>), PrefillSmem<128>::BYTES, attr_bit<T>(ATTR_PREFILL), "prefill");
         if (rc) return rc;
     } else if (D == 64) {
-        const int rc = raise_lds(reinterpret_cast<const void*>(&prefill_kernel<64>), PrefillSmem<64>::BYTES, ATTR_PREFILL_64, "prefill (head_dim 64)");
+        const int rc = raise_lds(reinterpret_cast<const void*>(&prefill_kernel<T, 64>), PrefillSmem<64>::BYTES, attr_bit<T>(ATTR_PREFILL_64), "prefill (head_dim 64)");
         if (rc) return rc;
     }
     PrefillParams p{};
-    p.q = static_cast<const _Float16*>(q);
-    p.k = static_cast<const _Float16*>(k);
-    p.v = static_cast<const _Float16*>(v);
-    p.o = static_cast<_Float16*>(out);
+    p.q = static_cast<const e16*>(q);
+    p.k = static_cast<const e16*>(k);
+    p.v = static_cast<const e16*>(v);
+    p.o = static_cast<e16*>(out);
     p.q_st = q_stride_tok;
     p.q_sh = q_stride_head;
     p.k_st = k_stride_tok;
@@ -1874,15 +1946,115 @@ extern "C" int deft_prefill_f16(const void* q, int64_t q_stride_tok, int64_t q_s
         return DEFT_EINVAL;
     }
     const dim3 grid((unsigned)((int64_t)p.nblk * Hq * batch));
-    if (D == 128) hipLaunchKernelGGL((prefill_kernel<128>), grid, dim3(512), PrefillSmem<128>::BYTES, static_cast<hipStream_t>(stream), p);
-    else if (D == 64) hipLaunchKernelGGL((prefill_kernel<64>), grid, dim3(512), PrefillSmem<64>::BYTES, static_cast<hipStream_t>(stream), p);
+    if (D == 128) hipLaunchKernelGGL((prefill_kernel<T, 128>), grid, dim3(512), PrefillSmem<128>::BYTES, static_cast<hipStream_t>(stream), p);
+    else if (D == 64) hipLaunchKernelGGL((prefill_kernel<T, 64>), grid, dim3(512), PrefillSmem<64>::BYTES, static_cast<hipStream_t>(stream), p);
     else {  // head_dim 32 / 16: a wave per (token, head)
         const dim3 g2((unsigned)((((int64_t)p.nblk * 256 + 3) / 4) * batch), (unsigned)Hq);
-        if (D == 32) hipLaunchKernelGGL((prefill_small_kernel<32>), g2, dim3(256), 0, static_cast<hipStream_t>(stream), p);
-        else hipLaunchKernelGGL((prefill_small_kernel<16>), g2, dim3(256), 0, static_cast<hipStream_t>(stream), p);
+        if (D == 32) hipLaunchKernelGGL((prefill_small_kernel<T, 32>), g2, dim3(256), 0, static_cast<hipStream_t>(stream), p);
+        else hipLaunchKernelGGL((prefill_small_kernel<T, 16>), g2, dim3(256), 0, static_cast<hipStream_t>(stream), p);
     }
     return check_launch("prefill launch");
 }
+
+
+// ---------------------------------------------------------------------------
+// The data entry points of include/deft_amd.h: every one exists for IEEE binary16 (_f16) and for bfloat16 (_bf16),
+// the same parameter list, the same body instantiated for the element type.
+// ---------------------------------------------------------------------------
+#define DEFT_TWINS(name, params, args)                                        \
+    extern "C" int deft_##name##_f16 params { return name##_t<F16> args; }    \
+    extern "C" int deft_##name##_bf16 params { return name##_t<BF16> args; }
+DEFT_TWINS(flatten_decode, (const void* q, int64_t q_stride_tok, int64_t q_stride_head, const void* k_base, const void*
+            v_base, int64_t kv_stride_slot, int64_t kv_stride_head, void* out, int64_t o_stride_tok, int64_t o_stride_head,
+            const int64_t* block_q, const int64_t* block_q_cnts, const int64_t* block_q_offset, const int64_t* block_bitmasks,
+            const int64_t* block_kv, const int64_t* block_lens, int NB, int P, int nq, int Hq, int Hkv, int D, float scale,
+            const void* plan, void* workspace, size_t workspace_bytes, void* stream), (q, q_stride_tok, q_stride_head, k_base,
+            v_base, kv_stride_slot, kv_stride_head, out, o_stride_tok, o_stride_head, block_q, block_q_cnts, block_q_offset,
+            block_bitmasks, block_kv, block_lens, NB, P, nq, Hq, Hkv, D, scale, plan, workspace, workspace_bytes, stream))
+DEFT_TWINS(flatten_decode_append, (const void* q, int64_t q_stride_tok, int64_t q_stride_head, void* k_base, void* v_base,
+            int64_t kv_stride_slot, int64_t kv_stride_head, void* out, int64_t o_stride_tok, int64_t o_stride_head, const
+            int64_t* block_q, const int64_t* block_q_cnts, const int64_t* block_q_offset, const int64_t* block_bitmasks, const
+            int64_t* block_kv, const int64_t* block_lens, int NB, int P, int nq, int Hq, int Hkv, int D, float scale, const
+            int32_t* cache_loc, const void* k_new, const void* v_new, int64_t new_stride_tok, int n_new, const void* plan,
+            void* workspace, size_t workspace_bytes, void* stream), (q, q_stride_tok, q_stride_head, k_base, v_base,
+            kv_stride_slot, kv_stride_head, out, o_stride_tok, o_stride_head, block_q, block_q_cnts, block_q_offset,
+            block_bitmasks, block_kv, block_lens, NB, P, nq, Hq, Hkv, D, scale, cache_loc, k_new, v_new, new_stride_tok,
+            n_new, plan, workspace, workspace_bytes, stream))
+DEFT_TWINS(node_decode, (const void* q, int64_t q_stride_tok, int64_t q_stride_head, const void* k_base, const void* v_base,
+            int64_t kv_stride_slot, int64_t kv_stride_head, void* out, int64_t o_stride_tok, int64_t o_stride_head, const
+            int64_t* node_kv, const int64_t* node_kv_offset, const int64_t* node_kv_len, const int64_t* node_q, const int64_t*
+            node_q_offset, const int64_t* node_q_len, int NE, int P, int64_t total_kv, int nq, int Hq, int Hkv, int D, float
+            scale, const void* plan, void* workspace, size_t workspace_bytes, void* stream), (q, q_stride_tok, q_stride_head,
+            k_base, v_base, kv_stride_slot, kv_stride_head, out, o_stride_tok, o_stride_head, node_kv, node_kv_offset,
+            node_kv_len, node_q, node_q_offset, node_q_len, NE, P, total_kv, nq, Hq, Hkv, D, scale, plan, workspace,
+            workspace_bytes, stream))
+DEFT_TWINS(node_decode_append, (const void* q, int64_t q_stride_tok, int64_t q_stride_head, void* k_base, void* v_base,
+            int64_t kv_stride_slot, int64_t kv_stride_head, void* out, int64_t o_stride_tok, int64_t o_stride_head, const
+            int64_t* node_kv, const int64_t* node_kv_offset, const int64_t* node_kv_len, const int64_t* node_q, const int64_t*
+            node_q_offset, const int64_t* node_q_len, int NE, int P, int64_t total_kv, int nq, int Hq, int Hkv, int D, float
+            scale, const int32_t* cache_loc, const void* k_new, const void* v_new, int64_t new_stride_tok, int n_new, const
+            void* plan, void* workspace, size_t workspace_bytes, void* stream), (q, q_stride_tok, q_stride_head, k_base,
+            v_base, kv_stride_slot, kv_stride_head, out, o_stride_tok, o_stride_head, node_kv, node_kv_offset, node_kv_len,
+            node_q, node_q_offset, node_q_len, NE, P, total_kv, nq, Hq, Hkv, D, scale, cache_loc, k_new, v_new,
+            new_stride_tok, n_new, plan, workspace, workspace_bytes, stream))
+DEFT_TWINS(flatten_decode_rope_append, (const void* q, int64_t q_stride_tok, int64_t q_stride_head, void* k_base, void*
+            v_base, int64_t kv_stride_slot, int64_t kv_stride_head, void* out, int64_t o_stride_tok, int64_t o_stride_head,
+            const int64_t* block_q, const int64_t* block_q_cnts, const int64_t* block_q_offset, const int64_t* block_bitmasks,
+            const int64_t* block_kv, const int64_t* block_lens, int NB, int P, int nq, int Hq, int Hkv, int D, float scale,
+            const int32_t* cache_loc, const void* k_new, const void* v_new, int64_t new_stride_tok, int n_new, const float*
+            cos_sin_rows, int rotary_dim, int is_neox_style, const void* plan, void* workspace, size_t workspace_bytes, void*
+            stream), (q, q_stride_tok, q_stride_head, k_base, v_base, kv_stride_slot, kv_stride_head, out, o_stride_tok,
+            o_stride_head, block_q, block_q_cnts, block_q_offset, block_bitmasks, block_kv, block_lens, NB, P, nq, Hq, Hkv, D,
+            scale, cache_loc, k_new, v_new, new_stride_tok, n_new, cos_sin_rows, rotary_dim, is_neox_style, plan, workspace,
+            workspace_bytes, stream))
+DEFT_TWINS(node_decode_rope_append, (const void* q, int64_t q_stride_tok, int64_t q_stride_head, void* k_base, void* v_base,
+            int64_t kv_stride_slot, int64_t kv_stride_head, void* out, int64_t o_stride_tok, int64_t o_stride_head, const
+            int64_t* node_kv, const int64_t* node_kv_offset, const int64_t* node_kv_len, const int64_t* node_q, const int64_t*
+            node_q_offset, const int64_t* node_q_len, int NE, int P, int64_t total_kv, int nq, int Hq, int Hkv, int D, float
+            scale, const int32_t* cache_loc, const void* k_new, const void* v_new, int64_t new_stride_tok, int n_new, const
+            float* cos_sin_rows, int rotary_dim, int is_neox_style, const void* plan, void* workspace, size_t workspace_bytes,
+            void* stream), (q, q_stride_tok, q_stride_head, k_base, v_base, kv_stride_slot, kv_stride_head, out, o_stride_tok,
+            o_stride_head, node_kv, node_kv_offset, node_kv_len, node_q, node_q_offset, node_q_len, NE, P, total_kv, nq, Hq,
+            Hkv, D, scale, cache_loc, k_new, v_new, new_stride_tok, n_new, cos_sin_rows, rotary_dim, is_neox_style, plan,
+            workspace, workspace_bytes, stream))
+DEFT_TWINS(prefill, (const void* q, int64_t q_stride_tok, int64_t q_stride_head, const void* k, int64_t k_stride_tok, int64_t
+            k_stride_head, const void* v, int64_t v_stride_tok, int64_t v_stride_head, void* out, int64_t o_stride_tok,
+            int64_t o_stride_head, const int32_t* b_start_loc, const int32_t* b_seq_len, int batch, int max_input_len, int Hq,
+            int Hkv, int D, float scale, void* stream), (q, q_stride_tok, q_stride_head, k, k_stride_tok, k_stride_head, v,
+            v_stride_tok, v_stride_head, out, o_stride_tok, o_stride_head, b_start_loc, b_seq_len, batch, max_input_len, Hq,
+            Hkv, D, scale, stream))
+DEFT_TWINS(rope_qk, (void* q, int64_t q_stride_tok, int64_t q_stride_head, int Hq, void* k, int64_t k_stride_tok, int64_t
+            k_stride_head, int Hk, const int64_t* positions, const float* cos_sin_cache, int64_t cache_stride, int n, int D,
+            int rotary_dim, int is_neox_style, void* stream), (q, q_stride_tok, q_stride_head, Hq, k, k_stride_tok,
+            k_stride_head, Hk, positions, cos_sin_cache, cache_stride, n, D, rotary_dim, is_neox_style, stream))
+DEFT_TWINS(seq_decode, (const void* q, int64_t q_stride_tok, int64_t q_stride_head, const void* k_base, const void* v_base,
+            int64_t kv_stride_slot, int64_t kv_stride_head, void* out, int64_t o_stride_tok, int64_t o_stride_head, const
+            void* plan, int nq, int64_t total_tokens, int Hq, int Hkv, int D, float scale, void* workspace, size_t
+            workspace_bytes, void* stream), (q, q_stride_tok, q_stride_head, k_base, v_base, kv_stride_slot, kv_stride_head,
+            out, o_stride_tok, o_stride_head, plan, nq, total_tokens, Hq, Hkv, D, scale, workspace, workspace_bytes, stream))
+DEFT_TWINS(seq_decode_append, (const void* q, int64_t q_stride_tok, int64_t q_stride_head, void* k_base, void* v_base, int64_t
+            kv_stride_slot, int64_t kv_stride_head, void* out, int64_t o_stride_tok, int64_t o_stride_head, const void* plan,
+            int nq, int64_t total_tokens, int Hq, int Hkv, int D, float scale, const int32_t* cache_loc, const void* k_new,
+            const void* v_new, int64_t new_stride_tok, int n_new, void* workspace, size_t workspace_bytes, void* stream), (q,
+            q_stride_tok, q_stride_head, k_base, v_base, kv_stride_slot, kv_stride_head, out, o_stride_tok, o_stride_head,
+            plan, nq, total_tokens, Hq, Hkv, D, scale, cache_loc, k_new, v_new, new_stride_tok, n_new, workspace,
+            workspace_bytes, stream))
+extern "C" int deft_kv_append_f16(void* k_base, void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head, const int32_t* cache_loc,
+                                  const void* k_new, const void* v_new, int64_t new_stride_tok, int n, int Hkv, int D, void* stream) {
+    return kv_append_impl(k_base, v_base, kv_stride_slot, kv_stride_head, cache_loc, k_new, v_new, new_stride_tok, n, Hkv, D, stream);
+}
+extern "C" int deft_kv_append_bf16(void* k_base, void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head, const int32_t* cache_loc,
+                                   const void* k_new, const void* v_new, int64_t new_stride_tok, int n, int Hkv, int D, void* stream) {
+    return kv_append_impl(k_base, v_base, kv_stride_slot, kv_stride_head, cache_loc, k_new, v_new, new_stride_tok, n, Hkv, D, stream);
+}
+DEFT_TWINS(flatten_stage1, (const void* q, int64_t q_stride_tok, int64_t q_stride_head, const void* k_base, const void*
+            v_base, int64_t kv_stride_slot, int64_t kv_stride_head, const int64_t* block_q, const int64_t* block_q_cnts, const
+            int64_t* block_q_offset, const int64_t* block_bitmasks, const int64_t* block_kv, const int64_t* block_lens, int
+            NB, int P, int nq, int Hq, int Hkv, int D, float scale, const void* plan, void* workspace, size_t workspace_bytes,
+            void* stream), (q, q_stride_tok, q_stride_head, k_base, v_base, kv_stride_slot, kv_stride_head, block_q,
+            block_q_cnts, block_q_offset, block_bitmasks, block_kv, block_lens, NB, P, nq, Hq, Hkv, D, scale, plan, workspace,
+            workspace_bytes, stream))
+#undef DEFT_TWINS
 
 
 // ---------------------------------------------------------------------------

@@ -2,7 +2,7 @@
 // (the reference: tree_attention.py:296-546, two kernels with fp32 / fp16 atomics and a host-side div_).
 //
 // Deterministic gather: the wave lists the partial rows of its query in ascending row order (scan of row_q, ordered
-// ballots), takes the TRUE maximum of their log-sum-exps, accumulates in fp32 in list order and rounds to fp16 once.
+// ballots), takes the TRUE maximum of their log-sum-exps, accumulates in fp32 in list order and rounds to the element type (fp16 or bf16) once.
 // Used by the stand-alone merge kernel (merge_kernel, deft_kernels.hip) and by the merge waves at the end of the
 // single-launch decode kernel (stage1_np.h) -- same code, same bits.
 //
@@ -115,9 +115,20 @@ __device__ inline void merge_accumulate(MergeState (&st)[NH], const __amdgpu_buf
     }
 }
 
-// Sum the row groups of the wave and write the pair's output row (fp16, one rounding).
-template <int D>
-__device__ inline void merge_finish(const MergeState& st, _Float16* dst, int lane) {
+// Four consecutive output elements from fp32, one rounding each; two 4-byte stores (output rows are only 4-byte aligned
+// by contract).
+template <class T>
+__device__ __forceinline__ void store_row4(e16* dst, float x0, float x1, float x2, float x3) {
+    using vec2 = typename T::vec2;
+    vec2 lo = {T::from_float(x0), T::from_float(x1)};
+    vec2 hi = {T::from_float(x2), T::from_float(x3)};
+    *reinterpret_cast<vec2*>(dst) = lo;
+    *reinterpret_cast<vec2*>(dst + 2) = hi;
+}
+
+// Sum the row groups of the wave and write the pair's output row (element type T, one rounding).
+template <class T, int D>
+__device__ inline void merge_finish(const MergeState& st, e16* dst, int lane) {
     constexpr int LPR = D / 4;
     floatx4 a = st.acc;
 #pragma unroll
@@ -126,10 +137,7 @@ __device__ inline void merge_finish(const MergeState& st, _Float16* dst, int lan
         for (int e = 0; e < 4; ++e) a[e] += __shfl_xor(a[e], off);
     if (lane < LPR) {
         const float inv = st.L > 0.f ? 1.f / st.L : 0.f;
-        half2v lo = {(_Float16)(a[0] * inv), (_Float16)(a[1] * inv)};
-        half2v hi = {(_Float16)(a[2] * inv), (_Float16)(a[3] * inv)};
-        *reinterpret_cast<half2v*>(dst + 4 * lane) = lo;  // output rows are only 4-byte aligned by contract
-        *reinterpret_cast<half2v*>(dst + 4 * lane + 2) = hi;
+        store_row4<T>(dst + 4 * lane, a[0] * inv, a[1] * inv, a[2] * inv, a[3] * inv);
     }
 }
 
@@ -141,9 +149,9 @@ __device__ inline void merge_finish(const MergeState& st, _Float16* dst, int lan
 // One query, NH heads (hq0, hq0 + hq_step, ...; those >= Hq are skipped), start to finish: rows of the query from
 // row_q (list area of `cap` ints in LDS, longer lists in further passes), merge, store.  `have` >= 0:
 // list[0 .. min(have, cap)) already holds the scan.
-template <int D, int CP, int NH>
+template <class T, int D, int CP, int NH>
 __device__ inline void merge_heads_wave(const float* partial_o, const float* partial_lse, const int32_t* row_q, int64_t rows,
-                                        int q, int hq0, int hq_step, int Hq, int* list, int cap, int have, _Float16* out_q,
+                                        int q, int hq0, int hq_step, int Hq, int* list, int cap, int have, e16* out_q,
                                         int64_t o_sh, int lane) {
     __amdgpu_buffer_rsrc_t po[NH], ls[NH];
     MergeState st[NH];
@@ -167,7 +175,7 @@ __device__ inline void merge_heads_wave(const float* partial_o, const float* par
     }
 #pragma unroll
     for (int h = 0; h < NH; ++h)
-        if (hq0 + h * hq_step < Hq) merge_finish<D>(st[h], out_q + (int64_t)(hq0 + h * hq_step) * o_sh, lane);
+        if (hq0 + h * hq_step < Hq) merge_finish<T, D>(st[h], out_q + (int64_t)(hq0 + h * hq_step) * o_sh, lane);
 }
 
 }  // namespace deft

@@ -5,8 +5,8 @@
 // Replaces context_attention_fwd (DeFT/deft/layers/attention/context_flashattention_nopad.py:130-195; kernel :12-127)
 // behind DeFTAttention.prefill_forward_triton (deft_attention.py:50-70): a batch of sequences packed without padding,
 // q[T, Hq, D], k / v[T, Hkv, D], token i of sequence b attends to tokens 0..i of b.  Compute-bound (MFMA), unlike the
-// decode path; arithmetic as there: fp16 operands, fp32 accumulation, scale 1/sqrt(D) after the dot, fp32 online
-// softmax, P rounded to fp16 for the PV product with row sums over the ROUNDED values, one fp16 rounding at the end.
+// decode path; arithmetic as there: fp16 or bf16 operands (the element traits T of deft_kernels.hip), fp32 accumulation, scale 1/sqrt(D) after the dot, fp32 online
+// softmax, P rounded to the element type for the PV product, one rounding of the output at the end.
 //
 //   * one workgroup = 8 waves = 256 consecutive queries of one (sequence, query head); wave w owns queries 32w..32w+31;
 //   * K / V tiles of 128 keys are staged in LDS by LDS-DMA, double buffered: while a tile is consumed the next one
@@ -26,10 +26,10 @@
 namespace deft {
 
 struct PrefillParams {
-    const _Float16* q;
-    const _Float16* k;
-    const _Float16* v;
-    _Float16* o;
+    const e16* q;
+    const e16* k;
+    const e16* v;
+    e16* o;
     int64_t q_st, q_sh, k_st, k_sh, v_st, v_sh, o_st, o_sh;  // elements
     const int32_t* b_start_loc;
     const int32_t* b_seq_len;
@@ -49,8 +49,10 @@ struct PrefillSmem {
     static_assert(BYTES <= 160 * 1024, "LDS budget");
 };
 
-template <int D>
+template <class T, int D>
 __global__ __launch_bounds__(512, 1) void prefill_kernel(PrefillParams p) {
+    using vec8 = typename T::vec8;
+    using vec4 = typename T::vec4;
     constexpr int KS = D / 16;   // k-steps of QK^T
     constexpr int CH = D / 8;    // 16-byte chunks per row
     constexpr int NB = D / 32;   // 32-wide column blocks of O^T
@@ -130,11 +132,11 @@ __global__ __launch_bounds__(512, 1) void prefill_kernel(PrefillParams p) {
     // ---- this lane's query and its Q fragments (B operand: 8 halves at d = 16 ks + 8 h) ----------------------
     const int qi = m * QB + 32 * w + c;  // query index inside the sequence
     const int qrow = qi < len ? qi : len - 1;
-    half8 qf[KS];
+    vec8 qf[KS];
     {
-        const _Float16* qp = p.q + (start + qrow) * p.q_st + (int64_t)head * p.q_sh + 8 * h;
+        const e16* qp = p.q + (start + qrow) * p.q_st + (int64_t)head * p.q_sh + 8 * h;
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) qf[ks] = *reinterpret_cast<const half8*>(qp + 16 * ks);
+        for (int ks = 0; ks < KS; ++ks) qf[ks] = *reinterpret_cast<const vec8*>(qp + 16 * ks);
     }
     // Q fragments and tile 0.  The empty asm statements make the compiler itself wait for the Q loads HERE: otherwise its
     // counter model carries "8 loads outstanding" into the tile loop and puts s_waitcnt vmcnt(7) .. vmcnt(0) in front of
@@ -190,19 +192,19 @@ __global__ __launch_bounds__(512, 1) void prefill_kernel(PrefillParams p) {
         const int kstage = SM::K_OFF + stg * SM::STAGE;
         // K fragments double-buffered by k-step: the four reads of k-step ks + 1 are issued BEFORE the four MFMAs of ks (left to
         // itself the compiler reads two fragments, waits, issues two MFMAs -- every pair of MFMAs behind an LDS round trip)
-        half8 af[2][4];
+        vec8 af[2][4];
 #pragma unroll
-        for (int kb = 0; kb < 4; ++kb) af[0][kb] = *reinterpret_cast<const half8*>(smem + (kfrag_b[0] + kstage) + 32 * kb * D * 2);
+        for (int kb = 0; kb < 4; ++kb) af[0][kb] = *reinterpret_cast<const vec8*>(smem + (kfrag_b[0] + kstage) + 32 * kb * D * 2);
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             if (ks + 1 < KS) {
                 const char* kp = smem + (kfrag_b[ks + 1] + kstage);
 #pragma unroll
-                for (int kb = 0; kb < 4; ++kb) af[(ks + 1) & 1][kb] = *reinterpret_cast<const half8*>(kp + 32 * kb * D * 2);
+                for (int kb = 0; kb < 4; ++kb) af[(ks + 1) & 1][kb] = *reinterpret_cast<const vec8*>(kp + 32 * kb * D * 2);
             }
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int kb = 0; kb < 4; ++kb) acc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[ks & 1][kb], qf[ks], acc[kb], 0, 0, 0);
+            for (int kb = 0; kb < 4; ++kb) acc[kb] = T::mfma(af[ks & 1][kb], qf[ks], acc[kb]);
             __builtin_amdgcn_sched_barrier(0);
         }
         PF_PHASE(2);
@@ -232,7 +234,7 @@ __global__ __launch_bounds__(512, 1) void prefill_kernel(PrefillParams p) {
         const float m_new = fmaxf(m_run, mx);
         const float msafe = (m_new == -INFINITY) ? 0.f : m_new;
         const float alpha = (m_run == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(m_run - msafe);
-        half8 pb[4][2];
+        vec8 pb[4][2];
         float sum = 0.f;
 #pragma unroll
         for (int kb = 0; kb < 4; ++kb)
@@ -245,8 +247,8 @@ __global__ __launch_bounds__(512, 1) void prefill_kernel(PrefillParams p) {
                 // chains would be packed into v_pk_add_f32, which is as bad)
                 const float e0 = __builtin_amdgcn_exp2f(__builtin_fmaf(acc[kb][r], p.scale_log2e, -msafe));
                 const float e1 = __builtin_amdgcn_exp2f(__builtin_fmaf(acc[kb][r + 1], p.scale_log2e, -msafe));
-                pb[kb][r >> 3][r & 7] = (_Float16)e0;
-                pb[kb][r >> 3][(r & 7) + 1] = (_Float16)e1;
+                pb[kb][r >> 3][r & 7] = T::from_float(e0);
+                pb[kb][r >> 3][(r & 7) + 1] = T::from_float(e1);
                 sum += e0;
                 sum += e1;
             }
@@ -270,7 +272,7 @@ __global__ __launch_bounds__(512, 1) void prefill_kernel(PrefillParams p) {
         typedef __attribute__((address_space(3))) short4v* lds_s4;
         union VFrag {
             short4v s4[2];
-            half8 h8;
+            vec8 h8;
         };
         VFrag vf[2][NB];
         auto load_group = [&](int g, VFrag (&dst)[NB]) {
@@ -289,7 +291,7 @@ __global__ __launch_bounds__(512, 1) void prefill_kernel(PrefillParams p) {
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int bk = 0; bk < NB; ++bk)
-                o[bk] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf[g & 1][bk].h8, pb[g >> 1][g & 1], o[bk], 0, 0, 0);
+                o[bk] = T::mfma(vf[g & 1][bk].h8, pb[g >> 1][g & 1], o[bk]);
             __builtin_amdgcn_sched_barrier(0);
         }
         PF_PHASE(4);
@@ -308,14 +310,14 @@ __global__ __launch_bounds__(512, 1) void prefill_kernel(PrefillParams p) {
     // ---- normalise and store: lane (c, h) holds d = 32 bk + 8 j + 4 h + (0..3) of query c ---------------------
     if (qi < len) {
         const float inv = l_run > 0.f ? 1.f / l_run : 0.f;
-        _Float16* op = p.o + (start + qi) * p.o_st + (int64_t)head * p.o_sh + 4 * h;
+        e16* op = p.o + (start + qi) * p.o_st + (int64_t)head * p.o_sh + 4 * h;
 #pragma unroll
         for (int bk = 0; bk < NB; ++bk)
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                half4 v4 = {(_Float16)(o[bk][4 * j] * inv), (_Float16)(o[bk][4 * j + 1] * inv),
-                            (_Float16)(o[bk][4 * j + 2] * inv), (_Float16)(o[bk][4 * j + 3] * inv)};
-                *reinterpret_cast<half4*>(op + 32 * bk + 8 * j) = v4;
+                vec4 v4 = {T::from_float(o[bk][4 * j] * inv), T::from_float(o[bk][4 * j + 1] * inv),
+                           T::from_float(o[bk][4 * j + 2] * inv), T::from_float(o[bk][4 * j + 3] * inv)};
+                *reinterpret_cast<vec4*>(op + 32 * bk + 8 * j) = v4;
             }
     }
 #ifdef DEFT_EXPERIMENTS
@@ -337,8 +339,9 @@ __global__ __launch_bounds__(512, 1) void prefill_kernel(PrefillParams p) {
 // head_dim 32 and 16 (context_flashattention_nopad.py:134 takes them; no model the reference ships has them): one wave per
 // (query token, query head), the lanes stride over the keys 0 .. i with a private online softmax in fp32 and merge at the end.
 // Correctness path, not a tuned one.  Grid: (ceil(max_input_len / 4) * batch, Hq), 256 threads.
-template <int D>
+template <class T, int D>
 __global__ __launch_bounds__(256) void prefill_small_kernel(PrefillParams p) {
+    using scalar = typename T::scalar;
     static_assert(D == 32 || D == 16, "small head dimensions");
     const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
     const int per_seq = (p.nblk * 256 + 3) / 4;  // (nblk * 256 >= max_input_len)
@@ -351,24 +354,24 @@ __global__ __launch_bounds__(256) void prefill_small_kernel(PrefillParams p) {
     const int64_t start = p.b_start_loc[b];
     const int kvh = head / p.G;
     float q[D];
-    const _Float16* qp = p.q + (start + qi) * p.q_st + (int64_t)head * p.q_sh;
+    const scalar* qp = reinterpret_cast<const scalar*>(p.q + (start + qi) * p.q_st + (int64_t)head * p.q_sh);
 #pragma unroll
-    for (int d = 0; d < D; ++d) q[d] = (float)qp[d];
+    for (int d = 0; d < D; ++d) q[d] = T::to_float(qp[d]);
     float m = -INFINITY, s = 0.f, acc[D];
 #pragma unroll
     for (int d = 0; d < D; ++d) acc[d] = 0.f;
     for (int j = l; j <= qi; j += 64) {
-        const _Float16* kp = p.k + (start + j) * p.k_st + (int64_t)kvh * p.k_sh;
-        const _Float16* vp = p.v + (start + j) * p.v_st + (int64_t)kvh * p.v_sh;
+        const scalar* kp = reinterpret_cast<const scalar*>(p.k + (start + j) * p.k_st + (int64_t)kvh * p.k_sh);
+        const scalar* vp = reinterpret_cast<const scalar*>(p.v + (start + j) * p.v_st + (int64_t)kvh * p.v_sh);
         float dot = 0.f;
 #pragma unroll
-        for (int d = 0; d < D; ++d) dot += q[d] * (float)kp[d];
+        for (int d = 0; d < D; ++d) dot += q[d] * T::to_float(kp[d]);
         const float x = dot * p.scale_log2e;
         const float mn = fmaxf(m, x);
         const float a = __builtin_amdgcn_exp2f(m - mn), e = __builtin_amdgcn_exp2f(x - mn);  // (exp2(-inf) = 0 the first time)
         s = s * a + e;
 #pragma unroll
-        for (int d = 0; d < D; ++d) acc[d] = acc[d] * a + e * (float)vp[d];
+        for (int d = 0; d < D; ++d) acc[d] = acc[d] * a + e * T::to_float(vp[d]);
         m = mn;
     }
     // merge the 64 lanes' states (lanes beyond the keys hold m = -inf, s = 0)
@@ -383,9 +386,9 @@ __global__ __launch_bounds__(256) void prefill_small_kernel(PrefillParams p) {
     }
     if (l == 0) {
         const float inv = s > 0.f ? 1.f / s : 0.f;
-        _Float16* op = p.o + (start + qi) * p.o_st + (int64_t)head * p.o_sh;
+        scalar* op = reinterpret_cast<scalar*>(p.o + (start + qi) * p.o_st + (int64_t)head * p.o_sh);
 #pragma unroll
-        for (int d = 0; d < D; ++d) op[d] = (_Float16)(acc[d] * inv);
+        for (int d = 0; d < D; ++d) op[d] = T::from_float(acc[d] * inv);
     }
 }
 

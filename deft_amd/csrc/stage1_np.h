@@ -15,7 +15,7 @@
 //     barrier between load and use, only its own counted s_waitcnt.  K(i+1) is issued as soon as QK^T(i) is done,
 //     V(i+1) after PV(i);
 //   * the softmax is wave-private as well: S^T = K Q^T puts the wave's 32 keys on the MFMA M dimension, so a lane
-//     holds 16 key scores of one query; P^T (fp16) stays in registers and IS the B operand of O^T += V^T P^T
+//     holds 16 key scores of one query; P^T (in the element type) stays in registers and IS the B operand of O^T += V^T P^T
 //     (the contraction order of keys is permuted identically on the V^T side, read with ds_read_b64_tr_b16);
 //     each wave keeps (m, l, O[128 x 32]) for its key subset over the whole chunk;
 //   * at the end the four waves merge their states through LDS (two barriers per WORKGROUP, not per tile) and write
@@ -44,8 +44,8 @@ struct NpParams {
     int skew_full;     // > 0: only the first 8 x skew_full workgroups take item = index; behind them the EVEN ones (index % 8 = XCD) take the remaining items, the odd ones none
 #endif
     // fused paged append (optional): rows whose plan offset has bit 63 set are read from k_new / v_new
-    const _Float16* k_new;
-    const _Float16* v_new;
+    const e16* k_new;
+    const e16* v_new;
     const int32_t* cache_loc;
     int64_t new_st;
     int n_new;
@@ -55,31 +55,33 @@ struct NpParams {
     const float* cos_sin;  // [n_new][D] fp32: cos(D/2) | sin(D/2) of new row j = query row j (deft_rope_gather_rows)
 };
 
-// o1 = x1 cos - x2 sin, o2 = x2 cos + x1 sin in fp32 without FMA contraction, one rounding to fp16: the arithmetic of
-// rope_qk_kernel (deft_kernels.hip) and of oracle/rope.py, so that the fused form is bit-identical to rope + decode.
-__device__ __forceinline__ void rope_pair(float x1, float x2, float cs, float sn, _Float16& o1, _Float16& o2) {
+// o1 = x1 cos - x2 sin, o2 = x2 cos + x1 sin in fp32 without FMA contraction, one rounding to the element type: the
+// arithmetic of rope_qk_kernel (deft_kernels.hip) and of oracle/rope.py, so that the fused form is bit-identical to rope + decode.
+template <class T>
+__device__ __forceinline__ void rope_pair(float x1, float x2, float cs, float sn, typename T::scalar& o1, typename T::scalar& o2) {
 #pragma clang fp contract(off)
     const float a = x1 * cs, b = x2 * sn, c = x2 * cs, d = x1 * sn;
-    o1 = (_Float16)(a - b);
-    o2 = (_Float16)(c + d);
+    o1 = T::from_float(a - b);
+    o2 = T::from_float(c + d);
 }
 
-// One 16-byte chunk (8 halves at d = 8 ch ..) of a row rotated against its partner chunk ch ^ 8 (d +- D/2):
+// One 16-byte chunk (8 elements at d = 8 ch ..) of a row rotated against its partner chunk ch ^ 8 (d +- D/2):
 // cs = cos values of d & (D/2 - 1), sn = the sines.
+template <class T>
 __device__ __forceinline__ uintx4 rope_chunk(uintx4 own_u, uintx4 par_u, bool first_half, floatx4 c0, floatx4 c1, floatx4 s0,
                                              floatx4 s1) {
     union {
         uintx4 u;
-        half8 h8;
+        typename T::vec8 h8;
     } own, par, res;
     own.u = own_u;
     par.u = par_u;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
         const float cs = e < 4 ? c0[e & 3] : c1[e & 3], sn = e < 4 ? s0[e & 3] : s1[e & 3];
-        _Float16 o1, o2;
-        if (first_half) rope_pair((float)own.h8[e], (float)par.h8[e], cs, sn, o1, o2);
-        else rope_pair((float)par.h8[e], (float)own.h8[e], cs, sn, o2, o1);
+        typename T::scalar o1, o2;
+        if (first_half) rope_pair<T>(T::to_float(own.h8[e]), T::to_float(par.h8[e]), cs, sn, o1, o2);
+        else rope_pair<T>(T::to_float(par.h8[e]), T::to_float(own.h8[e]), cs, sn, o2, o1);
         res.h8[e] = o1;
     }
     return res.u;
@@ -101,7 +103,7 @@ struct NpSmem {
     static constexpr int SLICE = 32 * D * 2;            // one wave's 32 keys of K (or V)
     static constexpr int K_OFF = 0;                     // [4][SLICE]
     static constexpr int V_OFF = 4 * SLICE;             // [4][SLICE]
-    static constexpr int Q_OFF = 8 * SLICE;             // Q rows [32][D] fp16, chunks XOR-ed by (row & 15)
+    static constexpr int Q_OFF = 8 * SLICE;             // Q rows [32][D] elements, chunks XOR-ed by (row & 15)
     static constexpr int AUX_OFF = Q_OFF + MQ * D * 2;  // per wave 2 slots x 512 B: int64 rowoff[32] | u32 vmask[32] | i32 qsrc[32]
     static constexpr int AUX_SLOT = 512;
     static constexpr int X_OFF = AUX_OFF + 4 * 2 * AUX_SLOT;  // float m[2][4][32], l[2][4][32] (per head of the row: two with head_dim 64)
@@ -132,8 +134,11 @@ struct NpSmem {
 //      the head_dim-128 kernel unchanged: the same DMA granules, the same LDS slices, the same fragment reads.  Only the
 //      arithmetic splits: k-steps 0-3 are head A's S^T, 4-7 head B's (two accumulators, two softmaxes), column blocks 0-1 of O^T
 //      take head A's probabilities, 2-3 head B's, and the epilogue writes two 64-float partial rows per virtual row.
-template <int D, bool ROPE, bool NT, bool PEEL = ROPE, bool HD2 = false, bool DYN = false>
+// T: the element type of q, the pool and the new rows (F16 / BF16, deft_kernels.hip); partial rows are fp32 either way.
+template <class T, int D, bool ROPE, bool NT, bool PEEL = ROPE, bool HD2 = false, bool DYN = false>
 __global__ __launch_bounds__(256, 2) void stage1_np_kernel(NpParams np) {
+    using scalar = typename T::scalar;
+    using vec8 = typename T::vec8;
     constexpr int KS = D / 16;
     constexpr int LPT = 32 * (D / 8) / 64;  // DMA instructions per wave per K (or V) slice
     static_assert(D == 128 && LPT == 8, "tile-parallel stage 1 is instantiated for 256-byte rows (head_dim 128, or two heads of 64)");
@@ -186,22 +191,22 @@ __global__ __launch_bounds__(256, 2) void stage1_np_kernel(NpParams np) {
             if constexpr (ROPE) {  // the k row enters the pool rotated: chunk ch pairs with chunk ch ^ 8 (d, d + D/2)
                 union {
                     uintx4 u;
-                    half8 h8;
+                    vec8 h8;
                 } own, par, res;
                 own.u = kk;
                 par.u = *reinterpret_cast<const uintx4*>(np.k_new + so + (ch < D / 16 ? D / 2 : -(D / 2)));
                 const float* cs = cs_row + 8 * (ch & (D / 16 - 1));
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
-                    _Float16 o1, o2;
-                    if (ch < D / 16) rope_pair((float)own.h8[e], (float)par.h8[e], cs[e], cs[D / 2 + e], o1, o2);
-                    else rope_pair((float)par.h8[e], (float)own.h8[e], cs[e], cs[D / 2 + e], o2, o1);
+                    scalar o1, o2;
+                    if (ch < D / 16) rope_pair<T>(T::to_float(own.h8[e]), T::to_float(par.h8[e]), cs[e], cs[D / 2 + e], o1, o2);
+                    else rope_pair<T>(T::to_float(par.h8[e]), T::to_float(own.h8[e]), cs[e], cs[D / 2 + e], o2, o1);
                     res.h8[e] = o1;
                 }
                 kk = res.u;
             }
-            *reinterpret_cast<uintx4*>(const_cast<_Float16*>(p.k) + d_o) = kk;
-            *reinterpret_cast<uintx4*>(const_cast<_Float16*>(p.v) + d_o) = vv;
+            *reinterpret_cast<uintx4*>(const_cast<e16*>(p.k) + d_o) = kk;
+            *reinterpret_cast<uintx4*>(const_cast<e16*>(p.v) + d_o) = vv;
         }
     }
 
@@ -435,7 +440,7 @@ __global__ __launch_bounds__(256, 2) void stage1_np_kernel(NpParams np) {
     issue_v();
 
     constexpr bool QF_LDS = HD2;  // Q fragments re-read from LDS every tile instead of living in 32 registers (with ROPE too it measured slower than three spilled registers: gqa_4kx32 fused 23.0 -> 24.3 us per layer)
-    half8 qf[QF_LDS ? 1 : KS];
+    vec8 qf[QF_LDS ? 1 : KS];
     float m_run[NH], l_run[NH];
 #pragma unroll
     for (int hh = 0; hh < NH; ++hh) m_run[hh] = -INFINITY, l_run[hh] = 0.f;
@@ -464,17 +469,17 @@ __global__ __launch_bounds__(256, 2) void stage1_np_kernel(NpParams np) {
                 const int row = 8 * w + 4 * i + dkey;
                 const int ch = dpos ^ (row & 15);
                 *reinterpret_cast<uintx4*>(smem + SM::Q_OFF + row * 256 + dpos * 16) =
-                    rope_chunk(own[i], par[i], ch < 8, rq[4 * i], rq[4 * i + 1], rq[4 * i + 2], rq[4 * i + 3]);
+                    rope_chunk<T>(own[i], par[i], ch < 8, rq[4 * i], rq[4 * i + 1], rq[4 * i + 2], rq[4 * i + 3]);
             }
         }
         lds_barrier();  // rotated Q rows of all four waves visible
         if constexpr (!QF_LDS) {
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks)
-                qf[ks] = *reinterpret_cast<const half8*>(smem + SM::Q_OFF + c * D * 2 + (((2 * ks + h) ^ (c & 15)) * 16));
+                qf[ks] = *reinterpret_cast<const vec8*>(smem + SM::Q_OFF + c * D * 2 + (((2 * ks + h) ^ (c & 15)) * 16));
             if (p.scale_log2e < 0.f)
 #pragma unroll
-                for (int ks = 0; ks < KS; ++ks) qf[ks] = -qf[ks];
+                for (int ks = 0; ks < KS; ++ks) qf[ks] = T::neg(qf[ks]);
         }
     }
     for (int i = 0; i < n; ++i) {
@@ -491,10 +496,10 @@ __global__ __launch_bounds__(256, 2) void stage1_np_kernel(NpParams np) {
             if constexpr (!QF_LDS) {
 #pragma unroll
                 for (int ks = 0; ks < KS; ++ks)
-                    qf[ks] = *reinterpret_cast<const half8*>(smem + SM::Q_OFF + c * D * 2 + (((2 * ks + h) ^ (c & 15)) * 16));
+                    qf[ks] = *reinterpret_cast<const vec8*>(smem + SM::Q_OFF + c * D * 2 + (((2 * ks + h) ^ (c & 15)) * 16));
                 if (p.scale_log2e < 0.f)
 #pragma unroll
-                    for (int ks = 0; ks < KS; ++ks) qf[ks] = -qf[ks];
+                    for (int ks = 0; ks < KS; ++ks) qf[ks] = T::neg(qf[ks]);
             }
         }
         if constexpr (ROPE) {
@@ -523,7 +528,7 @@ __global__ __launch_bounds__(256, 2) void stage1_np_kernel(NpParams np) {
                         const floatx4 s0 = *reinterpret_cast<const floatx4*>(cs + D / 2);
                         const floatx4 s1 = *reinterpret_cast<const floatx4*>(cs + D / 2 + 4);
                         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // both reads of every lane before any write
-                        *reinterpret_cast<uintx4*>(rowp + dpos * 16) = rope_chunk(own, par, ch < 8, c0, c1, s0, s1);
+                        *reinterpret_cast<uintx4*>(rowp + dpos * 16) = rope_chunk<T>(own, par, ch < 8, c0, c1, s0, s1);
                     }
                 }
             }
@@ -543,15 +548,15 @@ __global__ __launch_bounds__(256, 2) void stage1_np_kernel(NpParams np) {
         if (!ABL(1)) {  // experiments build: 1 skip QK^T, 4 skip PV, 16 skip the epilogue, 32 skip the stores
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
-                const half8 a = *reinterpret_cast<const half8*>(smem + krow_b + (kcol_b ^ (32 * ks)));
+                const vec8 a = *reinterpret_cast<const vec8*>(smem + krow_b + (kcol_b ^ (32 * ks)));
                 constexpr int HALF = KS / 2;
                 floatx16& dst = acc[HD2 ? (ks / HALF) : 0];
                 if constexpr (QF_LDS) {  // (the variants that are short of registers re-read the Q fragment: 32 VGPRs for 8 LDS reads a tile)
-                    half8 qk = *reinterpret_cast<const half8*>(smem + SM::Q_OFF + c * D * 2 + (((2 * ks + h) ^ (c & 15)) * 16));
-                    if (p.scale_log2e < 0.f) qk = -qk;
-                    dst = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, qk, dst, 0, 0, 0);
+                    vec8 qk = *reinterpret_cast<const vec8*>(smem + SM::Q_OFF + c * D * 2 + (((2 * ks + h) ^ (c & 15)) * 16));
+                    if (p.scale_log2e < 0.f) qk = T::neg(qk);
+                    dst = T::mfma(a, qk, dst);
                 } else {
-                    dst = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, qf[ks], dst, 0, 0, 0);
+                    dst = T::mfma(a, qf[ks], dst);
                 }
             }
         }
@@ -587,7 +592,7 @@ __global__ __launch_bounds__(256, 2) void stage1_np_kernel(NpParams np) {
         }
         PHASE(2);
         // ---- wave-private online softmax (per head of the row) ------------------------------------------------
-        half8 pb[NH][2];
+        vec8 pb[NH][2];
 #pragma unroll
         for (int hh = 0; hh < NH; ++hh) {
             const float mxx = max_xor32(mx[hh]) * sc;  // (rounded once, like every scaled score was: the same maximum as before)
@@ -597,9 +602,9 @@ __global__ __launch_bounds__(256, 2) void stage1_np_kernel(NpParams np) {
             float sum = 0.f;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const _Float16 ph = (_Float16)__builtin_amdgcn_exp2f(__builtin_fmaf(acc[hh][r], sc, -msafe));
+                const scalar ph = T::from_float(__builtin_amdgcn_exp2f(__builtin_fmaf(acc[hh][r], sc, -msafe)));  // ONE rounding, to nearest even
                 pb[hh][r >> 3][r & 7] = ph;
-                sum += (float)ph;  // row sums over the ROUNDED probabilities: the weights sum to 1 exactly
+                sum += T::to_float(ph);  // row sums over the ROUNDED probabilities: the weights sum to 1 exactly
             }
             sum = sum_xor32(sum);
             l_run[hh] = l_run[hh] * alpha + sum;
@@ -630,11 +635,11 @@ __global__ __launch_bounds__(256, 2) void stage1_np_kernel(NpParams np) {
                 const int vb = vtr_row_b + vtr_col_b[blk] + (16 * t) * D * 2;
                 union {
                     short4v s4[2];
-                    half8 h8;
+                    vec8 h8;
                 } av;
                 av.s4[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4)(uintptr_t)(vb));
                 av.s4[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4)(uintptr_t)(vb + 8 * D * 2));
-                o[blk] = __builtin_amdgcn_mfma_f32_32x32x16_f16(av.h8, pb[HD2 ? (blk >> 1) : 0][t], o[blk], 0, 0, 0);
+                o[blk] = T::mfma(av.h8, pb[HD2 ? (blk >> 1) : 0][t], o[blk]);
             }
         }
         if (has1) issue_v();  // V(i+1); rowoff still holds tile i+1's offsets

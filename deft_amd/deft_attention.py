@@ -19,7 +19,7 @@ from __future__ import annotations
 import torch
 from torch import nn
 
-from ._lib import DeftLibraryError, check, lib, tensor_version
+from ._lib import DeftLibraryError, check, entry, lib, same_elem_dtype, tensor_version
 from .forward_mode import ForwardMode, InputMetadata
 from .context_attention import context_attention_fwd
 from .token_attention import seq_append_attention, token_attention_fwd
@@ -49,8 +49,9 @@ class _DecodeStep:
         from .tree_attention import _flatten_plan, _node_plan
 
         kv0 = pool.kv_data[0]
-        if not (q.is_cuda and kv0.is_cuda and q.dtype == torch.float16 and kv0.dtype == torch.float16):
-            raise TypeError("decode step needs fp16 CUDA tensors")
+        if not (q.is_cuda and kv0.is_cuda):
+            raise TypeError("decode step needs CUDA tensors")
+        self.dtype = same_elem_dtype(q=q, kv_pool=kv0, k=k)  # fp16 or bf16, one type for q, pool, new rows and output
         self.mode, self.md, self.pool, self.cache_loc = mode, md, pool, cache_loc
         # (an inference tensor has no version counter, -1: the step is then identified by the objects alone -- a
         #  TreeMetadata and a cache_loc tensor are made anew every decode step)
@@ -77,8 +78,8 @@ class _DecodeStep:
                                       cache_loc=cache_loc, new_stride=self.k_stride)
             self.ws_bytes = lib.deft_flatten_workspace_bytes(self.NB, self.P, self.nq, Hq, Hkv, D)
             self.tail = (self.NB, self.P, self.nq, Hq, Hkv, D, self.scale)
-            self.fn = lib.deft_flatten_decode_append_f16
-            self.fn_rope = lib.deft_flatten_decode_rope_append_f16
+            self.fn = entry("deft_flatten_decode_append", self.dtype)[0]
+            self.fn_rope = entry("deft_flatten_decode_rope_append", self.dtype)[0]
         else:
             mdl = [md.node_kv, md.node_kv_offset, md.node_kv_len, md.node_q, md.node_q_offset, md.node_q_len]
             NE, P, total = md.node_kv_offset.shape[0], md.node_q.shape[0], md.node_kv.shape[0]
@@ -86,8 +87,8 @@ class _DecodeStep:
                                    cache_loc=cache_loc, new_stride=self.k_stride)
             self.ws_bytes = lib.deft_node_workspace_bytes(NE, P, total, self.nq, Hq, Hkv, D)
             self.tail = (NE, P, total, self.nq, Hq, Hkv, D, self.scale)
-            self.fn = lib.deft_node_decode_append_f16
-            self.fn_rope = lib.deft_node_decode_rope_append_f16
+            self.fn = entry("deft_node_decode_append", self.dtype)[0]
+            self.fn_rope = entry("deft_node_decode_rope_append", self.dtype)[0]
         for t in mdl:
             if t.dtype != torch.int64 or not t.is_cuda or not t.is_contiguous():
                 raise TypeError("TreeMetadata arrays must be contiguous int64 CUDA tensors")
@@ -98,24 +99,26 @@ class _DecodeStep:
         self.ws = {}  # raw stream -> workspace (calls on one stream are ordered; streams must not share scratch)
         self._rope_key, self._rope_rows = None, None
         nl = len(self.layer_ptrs)
-        self._o_all = torch.empty((nl, self.nq, Hq * D), dtype=torch.float16, device=self.device) if nl * self.nq * Hq * D <= (64 << 20) else None
+        self._o_all = torch.empty((nl, self.nq, Hq * D), dtype=self.dtype, device=self.device) if nl * self.nq * Hq * D <= (64 << 20) else None
         self._o_used = [False] * nl  # (a layer called twice within a step gets a fresh tensor the second time)
 
     def matches(self, mode, md, pool, cache_loc, q, k) -> bool:
         return (mode is self.mode and md is self.md and pool is self.pool and cache_loc is self.cache_loc
                 and tensor_version(cache_loc) == self.cache_loc_version and tuple(q.shape) == self.q_shape
-                and q.stride(0) == self.q_stride and k.stride(0) == self.k_stride and q.dtype == torch.float16)
+                and q.stride(0) == self.q_stride and k.stride(0) == self.k_stride and q.dtype == self.dtype)
 
     def run(self, layer_id: int, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, rope=None) -> torch.Tensor:
         """`rope` = (positions int64 [nq], cos_sin_cache fp32 [max_pos][rotary_dim], rotary_dim, is_neox_style): q and k are
-        the UNROTATED rows; the rotation happens inside the stage-1 launch (deft_*_decode_rope_append_f16)."""
+        the UNROTATED rows; the rotation happens inside the stage-1 launch (deft_*_decode_rope_append_f16 / _bf16)."""
         Hq, D = self.Hq, self.D
-        if q.stride(1) != 1 or k.stride(1) != 1 or v.stride(1) != 1 or v.stride(0) != self.k_stride or k.dtype != torch.float16:
-            raise ValueError("q / k / v rows must be contiguous fp16, k and v with the same row stride")
+        if q.stride(1) != 1 or k.stride(1) != 1 or v.stride(1) != 1 or v.stride(0) != self.k_stride:
+            raise ValueError("q / k / v rows must be contiguous, k and v with the same row stride")
+        if q.dtype != self.dtype or k.dtype != self.dtype or v.dtype != self.dtype:
+            raise TypeError(f"q / k / v must be {self.dtype} like the KV pool, got {q.dtype} / {k.dtype} / {v.dtype}")
         # outputs of the step's layers are rows of ONE allocation made with the step (a step object lives for one decode
         # step, so nothing is overwritten): saves an allocator round trip per layer call
         if self._o_all is None or layer_id >= self._o_all.shape[0] or self._o_used[layer_id]:
-            o = torch.empty((self.nq, Hq * D), dtype=torch.float16, device=self.device)
+            o = torch.empty((self.nq, Hq * D), dtype=self.dtype, device=self.device)
         else:
             o = self._o_all[layer_id]
             self._o_used[layer_id] = True

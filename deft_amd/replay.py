@@ -198,7 +198,7 @@ class TemplateReplay:
 
     def __init__(self, num_heads: int, num_kv_heads: int, head_dim: int, layers: int, mode: str = "flatten",
                  device: str = "cuda", attention: bool = True, seed: int = 0, vocab: int = 4096, session: Optional[bool] = None,
-                 capture_after="auto", incremental: bool = True, win_tiles: Optional[int] = None) -> None:
+                 capture_after="auto", incremental: bool = True, win_tiles: Optional[int] = None, dtype=torch.float16) -> None:
         """`session`: drive the attention path through `deft_amd.DecodeSession` -- the whole decode step (tree advance,
         TreeMetadata, plan, every layer's append + attention) as ONE captured hipGraph per structural epoch of the tree -- instead
         of the reference-shaped eager calls (`tree.alloc()`, `TreeMetadata.from_tree_cache`, `DeFTAttention.forward` per layer).
@@ -206,6 +206,7 @@ class TemplateReplay:
         `capture_after`: DecodeSession's -- how many steps of an epoch run eagerly before its step is captured.
         `incremental`: DecodeSession's -- window plans (most steps patch the plan instead of rebuilding metadata and plan)."""
         self.capture_after, self.incremental, self.win_tiles = capture_after, incremental, win_tiles
+        self.dtype = dtype  # element type of the pool, q / k / v and the outputs: float16 or bfloat16
         self.Hq, self.Hkv, self.D, self.layers = num_heads, num_kv_heads, head_dim, layers
         self.mode = mode
         # (node / node_chunk set BLOCK_CONFIG["MAX_BLOCK_LEN"] as the CLI does -- a process-wide setting.  The replay keeps ITS value
@@ -244,7 +245,7 @@ class TemplateReplay:
 
     def _pools(self, max_tokens: int, max_leaves: int):
         req = ReqToTokenPool(max_leaves + 8, max_tokens + 8, device=self.device)
-        pool = TokenToKVPool(max_tokens, torch.float16, self.Hkv, self.D, self.layers if self.attention else 0,
+        pool = TokenToKVPool(max_tokens, self.dtype, self.Hkv, self.D, self.layers if self.attention else 0,
                              device=self.device)
         return req, pool
 
@@ -284,7 +285,7 @@ class TemplateReplay:
                 budget = template.root_width * max_gen_len
             max_tokens = prompt_len + budget + max_leaves + 1024
         req, pool = self._pools(max_tokens, max_leaves)
-        tree = TreeCache(torch.float16, self.Hkv, self.D, self.layers, req, pool, None, True, False)
+        tree = TreeCache(self.dtype, self.Hkv, self.D, self.layers, req, pool, None, True, False)
         rep = ReplayReport(task=task, mode=self.mode, prompt_len=prompt_len)
         dev = self.device
         if self.attention:
@@ -292,9 +293,9 @@ class TemplateReplay:
             g.manual_seed(1)
             for l in range(self.layers):  # prefill stand-in: the prompt's KV is whatever the pool holds
                 pool._storage[l].normal_(generator=g)
-            q_all = torch.randn((self.layers, max_rows, self.Hq * self.D), dtype=torch.float16, device=dev, generator=g)
-            k_all = torch.randn((self.layers, max_rows, self.Hkv * self.D), dtype=torch.float16, device=dev, generator=g)
-            v_all = torch.randn((self.layers, max_rows, self.Hkv * self.D), dtype=torch.float16, device=dev, generator=g)
+            q_all = torch.randn((self.layers, max_rows, self.Hq * self.D), dtype=self.dtype, device=dev, generator=g)
+            k_all = torch.randn((self.layers, max_rows, self.Hkv * self.D), dtype=self.dtype, device=dev, generator=g)
+            v_all = torch.randn((self.layers, max_rows, self.Hkv * self.D), dtype=self.dtype, device=dev, generator=g)
         sess = None
         nq_now = [1]
         if self.session:

@@ -3,7 +3,7 @@
 Mirrors DeFT/deft/layers/rotary_embedding.py:75-180 for the configuration the reference's Llama uses
 (`get_rope(head_dim, rotary_dim=head_dim, max_position, base, rope_scaling=None, dtype=float32)`, llama2.py:86-93):
 same constructor arguments, same fp32 `cos_sin_cache` buffer, `forward(positions, query, key)` rotates query and key
-IN PLACE and returns them, like `forward_cuda` (:157-177).  The rotation runs in libdeft_amd.so (deft_rope_qk_f16);
+IN PLACE and returns them, like `forward_cuda` (:157-177).  The rotation runs in libdeft_amd.so (deft_rope_qk_f16 / deft_rope_qk_bf16 by the tensors' dtype);
 there is no PyTorch fallback.  Scaled variants (linear / dynamic NTK / YaRN, :183-650) are out of scope.
 """
 from __future__ import annotations
@@ -13,7 +13,7 @@ from typing import Optional, Tuple
 import torch
 from torch import nn
 
-from ._lib import DeftLibraryError, check, lib
+from ._lib import DeftLibraryError, check, entry, same_elem_dtype
 
 __all__ = ["RotaryEmbedding", "get_rope"]
 
@@ -33,10 +33,9 @@ class RotaryEmbedding(nn.Module):
     @torch.inference_mode()
     def forward(self, positions: torch.Tensor, query: torch.Tensor, key: torch.Tensor,
                 offsets: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        same_elem_dtype(query=query, key=key)
         if not query.is_cuda:
             raise DeftLibraryError("RotaryEmbedding needs CUDA (ROCm) tensors; deft_amd has no CPU path")
-        if query.dtype != torch.float16 or key.dtype != torch.float16:
-            raise TypeError("query / key must be float16")
         if offsets is not None:
             positions = positions + offsets
         positions = positions.flatten().to(torch.int64)
@@ -47,11 +46,11 @@ class RotaryEmbedding(nn.Module):
         k = key.view(n, -1, self.head_size)
         if q.stride(2) != 1 or k.stride(2) != 1:
             raise ValueError("query / key must have a contiguous head dimension")
-        check(lib.deft_rope_qk_f16(q.data_ptr(), q.stride(0), q.stride(1), q.shape[1], k.data_ptr(), k.stride(0), k.stride(1),
-                                   k.shape[1], positions.data_ptr(), self.cos_sin_cache.data_ptr(),
-                                   self.cos_sin_cache.stride(0), n, self.head_size, self.rotary_dim,
-                                   1 if self.is_neox_style else 0, torch.cuda.current_stream(query.device).cuda_stream),
-              "deft_rope_qk_f16")
+        fn, fn_name = entry("deft_rope_qk", query.dtype)
+        check(fn(q.data_ptr(), q.stride(0), q.stride(1), q.shape[1], k.data_ptr(), k.stride(0), k.stride(1),
+                 k.shape[1], positions.data_ptr(), self.cos_sin_cache.data_ptr(),
+                 self.cos_sin_cache.stride(0), n, self.head_size, self.rotary_dim,
+                 1 if self.is_neox_style else 0, torch.cuda.current_stream(query.device).cuda_stream), fn_name)
         return query, key
 
     def forward_native(self, positions: torch.Tensor, query: torch.Tensor, key: torch.Tensor,

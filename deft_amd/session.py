@@ -33,7 +33,7 @@ from typing import Callable, Dict, List, Optional
 import numpy as np
 import torch
 
-from ._lib import check, lib
+from ._lib import check, elem_suffix, entry, lib, same_elem_dtype
 from .tree_cache import BLOCK_CONFIG, TreeCache, _DeviceTree, _FIELDS, _ptr
 
 __all__ = ["DecodeSession", "FlattenDecodeSession"]
@@ -134,6 +134,8 @@ class DecodeSession:
         # (the device WITH its index: torch.device("cuda") != torch.device("cuda:0"), and the page-table fold below compares devices --
         #  round 3: with the default "cuda" pool the fold never happened and every step carried an index_put)
         self.tree, self.pool, self.device = tree, pool, pool._storage.device
+        self.dtype = pool._storage.dtype  # the element type of the whole session: q, new rows and outputs share the pool's
+        elem_suffix(self.dtype, "the KV pool")
         self.Hq, self.Hkv, self.D, self.layers = num_heads, num_kv_heads, head_dim, layers
         self.qkv, self.max_q_len, self.use_graph = qkv, max_q_len, use_graph
         self.graphs: Dict[str, Optional[torch.cuda.CUDAGraph]] = {}
@@ -263,7 +265,7 @@ class DecodeSession:
                                                   self.patch_cap))
             if self.win < 0:
                 check(self.win, "deft_window_create")
-        self.out = [torch.empty((self.nq, Hq * D), dtype=torch.float16, device=dev) for _ in range(self.layers)]
+        self.out = [torch.empty((self.nq, Hq * D), dtype=self.dtype, device=dev) for _ in range(self.layers)]
         order = sorted(tree.leaves)
         self.leaf_handles = [tree.leaves[i] for i in order]
         self.leaf_reqs = np.asarray([tree.leaf_to_req[i] for i in order], dtype=np.int64)
@@ -301,12 +303,13 @@ class DecodeSession:
         stream = torch.cuda.current_stream(self.device).cuda_stream
         if self.mode == "flatten":
             mdl = [self.md_ptrs[k] for k in ("block_q", "block_q_cnts", "block_q_offset", "block_bitmasks", "block_kv", "block_lens")]
-            fn, tail = lib.deft_flatten_decode_append_f16, (self.NB, self.P, self.nq, Hq, Hkv, D, 1.0 / (D ** 0.5))
+            fn, tail = entry("deft_flatten_decode_append", self.dtype)[0], (self.NB, self.P, self.nq, Hq, Hkv, D, 1.0 / (D ** 0.5))
         else:
             mdl = [self.md_ptrs[k] for k in ("node_kv", "node_kv_offset", "node_kv_len", "node_q", "node_q_offset", "node_q_len")]
-            fn, tail = lib.deft_node_decode_append_f16, (self.NE, self.PN, self.TKV, self.nq, Hq, Hkv, D, 1.0 / (D ** 0.5))
+            fn, tail = entry("deft_node_decode_append", self.dtype)[0], (self.NE, self.PN, self.TKV, self.nq, Hq, Hkv, D, 1.0 / (D ** 0.5))
         for l in range(self.layers):
             q, k, v = self.qkv(l)
+            same_elem_dtype(kv_pool=kv0, q=q, k=k, v=v)
             kptr = self.pool.kv_data[l].data_ptr()
             check(fn(q.data_ptr(), q.stride(0), D, kptr, kptr + v_off, kv0.stride(0), kv0.stride(2), self.out[l].data_ptr(), Hq * D, D,
                      *mdl, *tail, self.cache_loc.data_ptr(), k.data_ptr(), v.data_ptr(), k.stride(0), self.nq, self.plan.data_ptr(),

@@ -15,7 +15,7 @@ from __future__ import annotations
 
 import torch
 
-from ._lib import DeftLibraryError, check, lib, tensor_version
+from ._lib import DeftLibraryError, check, entry, lib, same_elem_dtype, tensor_version
 from .tree_attention import _check_qkv, _stream_ptr
 
 __all__ = ["token_attention_fwd", "seq_append_attention"]
@@ -87,20 +87,21 @@ def token_attention_fwd(q, k_buffer, v_buffer, o, req_to_token, b_req_idx, b_sta
                      k_buffer.stride(0), stream)
     ws_bytes = lib.deft_seq_workspace_bytes(nq, total, Hq, Hkv, D)
     ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=q.device)
-    check(lib.deft_seq_decode_f16(q.data_ptr(), q.stride(0), q.stride(1), k_buffer.data_ptr(), v_buffer.data_ptr(),
-                                  k_buffer.stride(0), k_buffer.stride(1), o.data_ptr(), o.stride(0), o.stride(1),
-                                  plan.data_ptr(), nq, total, Hq, Hkv, D, 1.0 / (D ** 0.5), ws.data_ptr(), ws_bytes, stream),
-          "deft_seq_decode_f16")
+    fn, fn_name = entry("deft_seq_decode", q.dtype)
+    check(fn(q.data_ptr(), q.stride(0), q.stride(1), k_buffer.data_ptr(), v_buffer.data_ptr(),
+             k_buffer.stride(0), k_buffer.stride(1), o.data_ptr(), o.stride(0), o.stride(1),
+             plan.data_ptr(), nq, total, Hq, Hkv, D, 1.0 / (D ** 0.5), ws.data_ptr(), ws_bytes, stream), fn_name)
 
 
 @torch.inference_mode()
 def seq_append_attention(q, kv_layer, o, cache_loc, cache_k, cache_v, req_to_token, b_req_idx, b_start_loc, b_seq_len,
                          total_num_tokens) -> None:
     """`store_kv_cache` + `token_attention_fwd` in one launch sequence (radix_attention_forward,
-    deft_attention.py:153-188); kv_layer is one layer of the pool, [size, 2, Hkv, D] fp16."""
+    deft_attention.py:153-188); kv_layer is one layer of the pool, [size, 2, Hkv, D] fp16 or bf16."""
     k_buffer, v_buffer = kv_layer[:, 0], kv_layer[:, 1]
     nq, Hq, Hkv, D, b_req_idx, b_start_loc, b_seq_len, total = _prep(q, k_buffer, v_buffer, o, req_to_token, b_req_idx,
                                                                      b_start_loc, b_seq_len, total_num_tokens)
+    same_elem_dtype(q=q, cache_k=cache_k, cache_v=cache_v)
     n = cache_loc.shape[0]
     k = cache_k.reshape(n, Hkv, D)
     v = cache_v.reshape(n, Hkv, D)
@@ -115,8 +116,9 @@ def seq_append_attention(q, kv_layer, o, cache_loc, cache_k, cache_v, req_to_tok
                      k_buffer.stride(0), stream, cache_loc=cache_loc, new_stride=k.stride(0))
     ws_bytes = lib.deft_seq_workspace_bytes(nq, total, Hq, Hkv, D)
     ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=q.device)
-    check(lib.deft_seq_decode_append_f16(q.data_ptr(), q.stride(0), q.stride(1), k_buffer.data_ptr(), v_buffer.data_ptr(),
-                                         k_buffer.stride(0), k_buffer.stride(1), o.data_ptr(), o.stride(0), o.stride(1),
-                                         plan.data_ptr(), nq, total, Hq, Hkv, D, 1.0 / (D ** 0.5),
-                                         cache_loc.data_ptr(), k.data_ptr(), v.data_ptr(), k.stride(0), n,
-                                         ws.data_ptr(), ws_bytes, stream), "deft_seq_decode_append_f16")
+    fn, fn_name = entry("deft_seq_decode_append", q.dtype)
+    check(fn(q.data_ptr(), q.stride(0), q.stride(1), k_buffer.data_ptr(), v_buffer.data_ptr(),
+             k_buffer.stride(0), k_buffer.stride(1), o.data_ptr(), o.stride(0), o.stride(1),
+             plan.data_ptr(), nq, total, Hq, Hkv, D, 1.0 / (D ** 0.5),
+             cache_loc.data_ptr(), k.data_ptr(), v.data_ptr(), k.stride(0), n,
+             ws.data_ptr(), ws_bytes, stream), fn_name)

@@ -13,14 +13,14 @@ functions keep no state, and temporaries come from torch's caching allocator —
 like the reference (:588-597, :307-312).  `output` is overwritten; the reference
 needs it pre-zeroed (:546), which is tolerated.
 
-There is no PyTorch or CPU fallback: tensors must be fp16 CUDA tensors and the
+There is no PyTorch or CPU fallback: tensors must be fp16 or bf16 CUDA tensors (one element type per call) and the
 HIP library must be loadable.
 """
 from __future__ import annotations
 
 import torch
 
-from ._lib import DeftLibraryError, check, lib, tensor_version
+from ._lib import DeftLibraryError, check, entry, lib, same_elem_dtype, tensor_version
 
 __all__ = ["tree_attention_subtree_fwd", "tree_attention_fwd", "flatten_append_attention", "kv_append",
            "flatten_stage1_partials"]
@@ -37,12 +37,11 @@ def _stream_ptr(t: torch.Tensor) -> int:
 
 
 def _check_qkv(query_states, key_buffer, value_buffer, output):
+    same_elem_dtype(query_states=query_states, key_buffer=key_buffer, value_buffer=value_buffer, output=output)
     for name, t in (("query_states", query_states), ("key_buffer", key_buffer), ("value_buffer", value_buffer),
                     ("output", output)):
         if not t.is_cuda:
             raise DeftLibraryError(f"{name} must be a CUDA (ROCm) tensor; deft_amd has no CPU path")
-        if t.dtype != torch.float16:
-            raise TypeError(f"{name} must be float16, got {t.dtype}")
         if t.dim() != 3 or t.stride(2) != 1:
             raise ValueError(f"{name} must be [n, heads, head_dim] with a contiguous head_dim")
     nq, Hq, D = query_states.shape
@@ -149,14 +148,15 @@ def tree_attention_subtree_fwd(
     scale = 1.0 / (D ** 0.5)  # tree_attention.py:601
     stream = _stream_ptr(query_states)
     plan = _flatten_plan(md, NB, P, Hq, Hkv, (query_states.stride(0), query_states.stride(1)), key_buffer.stride(0), stream)
-    rc = lib.deft_flatten_decode_f16(
+    fn, fn_name = entry("deft_flatten_decode", query_states.dtype)
+    rc = fn(
         query_states.data_ptr(), query_states.stride(0), query_states.stride(1),
         key_buffer.data_ptr(), value_buffer.data_ptr(), key_buffer.stride(0), key_buffer.stride(1),
         output.data_ptr(), output.stride(0), output.stride(1),
         *[t.data_ptr() for t in md],
         NB, P, nq, Hq, Hkv, D, scale, plan.data_ptr(), ws.data_ptr(), ws_bytes, stream,
     )
-    check(rc, "deft_flatten_decode_f16")
+    check(rc, fn_name)
 
 
 @torch.inference_mode()
@@ -165,7 +165,7 @@ def flatten_append_attention(query_states, kv_layer, output, cache_loc, cache_k,
     """`store_kv_cache` + `tree_attention_subtree_fwd` in ONE launch sequence
     (DeFTAttention.deft_flatten_forward, deft_attention.py:110-151): kv_layer[cache_loc, 0/1] = cache_k / cache_v
     and output = Flatten attention that already sees those rows.  kv_layer is one layer of the pool,
-    [size, 2, Hkv, D] fp16 (memory_pool.py:61-66)."""
+    [size, 2, Hkv, D] fp16 or bf16 (memory_pool.py:61-66)."""
     key_buffer, value_buffer = kv_layer[:, 0], kv_layer[:, 1]
     nq, Hq, Hkv, D = _check_qkv(query_states, key_buffer, value_buffer, output)
     if block_len != 128:
@@ -174,6 +174,7 @@ def flatten_append_attention(query_states, kv_layer, output, cache_loc, cache_k,
     md = [_i64(t, n) for t, n in ((block_q, "block_q"), (block_q_cnts, "block_q_cnts"),
                                   (block_q_offset, "block_q_offset"), (block_bitmasks, "block_bitmasks"),
                                   (block_kv, "block_kv"), (block_lens, "block_lens"))]
+    same_elem_dtype(query_states=query_states, cache_k=cache_k, cache_v=cache_v)
     n = cache_loc.shape[0]
     k = cache_k.reshape(n, Hkv, D)
     v = cache_v.reshape(n, Hkv, D)
@@ -188,7 +189,8 @@ def flatten_append_attention(query_states, kv_layer, output, cache_loc, cache_k,
     stream = _stream_ptr(query_states)
     plan = _flatten_plan(md, NB, P, Hq, Hkv, (query_states.stride(0), query_states.stride(1)), key_buffer.stride(0), stream,
                          cache_loc=cache_loc, new_stride=k.stride(0))
-    rc = lib.deft_flatten_decode_append_f16(
+    fn, fn_name = entry("deft_flatten_decode_append", query_states.dtype)
+    rc = fn(
         query_states.data_ptr(), query_states.stride(0), query_states.stride(1),
         key_buffer.data_ptr(), value_buffer.data_ptr(), key_buffer.stride(0), key_buffer.stride(1),
         output.data_ptr(), output.stride(0), output.stride(1),
@@ -197,7 +199,7 @@ def flatten_append_attention(query_states, kv_layer, output, cache_loc, cache_k,
         cache_loc.data_ptr(), k.data_ptr(), v.data_ptr(), k.stride(0), n,
         plan.data_ptr(), ws.data_ptr(), ws_bytes, stream,
     )
-    check(rc, "deft_flatten_decode_append_f16")
+    check(rc, fn_name)
 
 
 @torch.inference_mode()
@@ -226,14 +228,15 @@ def tree_attention_fwd(
     stream = _stream_ptr(query_states)
     plan = _node_plan(md, NE, P, total_kv, Hq, Hkv, (query_states.stride(0), query_states.stride(1)),
                       key_buffer.stride(0), stream)
-    rc = lib.deft_node_decode_f16(
+    fn, fn_name = entry("deft_node_decode", query_states.dtype)
+    rc = fn(
         query_states.data_ptr(), query_states.stride(0), query_states.stride(1),
         key_buffer.data_ptr(), value_buffer.data_ptr(), key_buffer.stride(0), key_buffer.stride(1),
         output.data_ptr(), output.stride(0), output.stride(1),
         *[t.data_ptr() for t in md],
         NE, P, total_kv, nq, Hq, Hkv, D, scale, plan.data_ptr(), ws.data_ptr(), ws_bytes, stream,
     )
-    check(rc, "deft_node_decode_f16")
+    check(rc, fn_name)
 
 
 @torch.inference_mode()
@@ -250,6 +253,7 @@ def node_append_attention(query_states, kv_layer, output, cache_loc, cache_k, ca
     md = [_i64(t, n) for t, n in ((KV_indices, "KV_indices"), (KV_indices_offset, "KV_indices_offset"),
                                   (KV_len, "KV_len"), (KVMapQ_List, "KVMapQ_List"),
                                   (KVMapQ_List_Offset, "KVMapQ_List_Offset"), (KVMapQ_List_Len, "KVMapQ_List_Len"))]
+    same_elem_dtype(query_states=query_states, cache_k=cache_k, cache_v=cache_v)
     n = cache_loc.shape[0]
     k = cache_k.reshape(n, Hkv, D)
     v = cache_v.reshape(n, Hkv, D)
@@ -264,7 +268,8 @@ def node_append_attention(query_states, kv_layer, output, cache_loc, cache_k, ca
     stream = _stream_ptr(query_states)
     plan = _node_plan(md, NE, P, total_kv, Hq, Hkv, (query_states.stride(0), query_states.stride(1)),
                       key_buffer.stride(0), stream, cache_loc=cache_loc, new_stride=k.stride(0))
-    rc = lib.deft_node_decode_append_f16(
+    fn, fn_name = entry("deft_node_decode_append", query_states.dtype)
+    rc = fn(
         query_states.data_ptr(), query_states.stride(0), query_states.stride(1),
         key_buffer.data_ptr(), value_buffer.data_ptr(), key_buffer.stride(0), key_buffer.stride(1),
         output.data_ptr(), output.stride(0), output.stride(1),
@@ -273,19 +278,20 @@ def node_append_attention(query_states, kv_layer, output, cache_loc, cache_k, ca
         cache_loc.data_ptr(), k.data_ptr(), v.data_ptr(), k.stride(0), n,
         plan.data_ptr(), ws.data_ptr(), ws_bytes, stream,
     )
-    check(rc, "deft_node_decode_append_f16")
+    check(rc, fn_name)
 
 
 @torch.inference_mode()
 def kv_append(kv_layer: torch.Tensor, cache_loc: torch.Tensor, cache_k: torch.Tensor, cache_v: torch.Tensor) -> None:
     """kv_layer[cache_loc, 0] = cache_k; kv_layer[cache_loc, 1] = cache_v in one launch.
 
-    kv_layer is one layer of the pool, [size, 2, Hkv, D] fp16 (memory_pool.py:61-66);
+    kv_layer is one layer of the pool, [size, 2, Hkv, D] fp16 or bf16 (memory_pool.py:61-66);
     semantics of KVCacheUpdater.update, paged branch (tree_cache.py:70-76)."""
+    same_elem_dtype(kv_layer=kv_layer, cache_k=cache_k, cache_v=cache_v)
     if not kv_layer.is_cuda:
         raise DeftLibraryError("kv_append needs a CUDA (ROCm) pool; deft_amd has no CPU path")
     size, two, Hkv, D = kv_layer.shape
-    assert two == 2 and kv_layer.dtype == torch.float16 and kv_layer.stride(3) == 1
+    assert two == 2 and kv_layer.stride(3) == 1
     n = cache_loc.shape[0]
     k = cache_k.reshape(n, Hkv, D)
     v = cache_v.reshape(n, Hkv, D)
@@ -297,11 +303,12 @@ def kv_append(kv_layer: torch.Tensor, cache_loc: torch.Tensor, cache_k: torch.Te
     if cache_loc.dtype != torch.int32:
         cache_loc = cache_loc.to(torch.int32)
     cache_loc = cache_loc.to(kv_layer.device)
-    rc = lib.deft_kv_append_f16(
+    fn, fn_name = entry("deft_kv_append", kv_layer.dtype)
+    rc = fn(
         kv_layer[:, 0].data_ptr(), kv_layer[:, 1].data_ptr(), kv_layer.stride(0), kv_layer.stride(2),
         cache_loc.data_ptr(), k.data_ptr(), v.data_ptr(), k.stride(0), n, Hkv, D, _stream_ptr(kv_layer),
     )
-    check(rc, "deft_kv_append_f16")
+    check(rc, fn_name)
 
 
 @torch.inference_mode()
@@ -309,20 +316,22 @@ def flatten_stage1_partials(query_states, key_buffer, value_buffer, block_q, blo
                             block_bitmasks, block_kv, block_lens):
     """Stage 1 only; returns (partial_o [Hq,P,D] f32, partial_lse [Hq,P] f32) like the
     reference's temporaries (tree_attention.py:588-597).  For tests and profiling."""
+    same_elem_dtype(query_states=query_states, key_buffer=key_buffer, value_buffer=value_buffer)
     nq, Hq, D = query_states.shape
     Hkv = key_buffer.shape[1]
     NB, P = block_q_cnts.shape[0], block_q.shape[0]
     ws_bytes = lib.deft_flatten_workspace_bytes(NB, P, nq, Hq, Hkv, D)
     ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=query_states.device)
     st = _stream_ptr(query_states)
-    rc = lib.deft_flatten_stage1_f16(
+    fn, fn_name = entry("deft_flatten_stage1", query_states.dtype)
+    rc = fn(
         query_states.data_ptr(), query_states.stride(0), query_states.stride(1),
         key_buffer.data_ptr(), value_buffer.data_ptr(), key_buffer.stride(0), key_buffer.stride(1),
         block_q.data_ptr(), block_q_cnts.data_ptr(), block_q_offset.data_ptr(), block_bitmasks.data_ptr(),
         block_kv.data_ptr(), block_lens.data_ptr(), NB, P, nq, Hq, Hkv, D, 1.0 / (D ** 0.5),
         None, ws.data_ptr(), ws_bytes, st,
     )
-    check(rc, "deft_flatten_stage1_f16")
+    check(rc, fn_name)
     po = torch.empty((Hq, P, D), dtype=torch.float32, device=query_states.device)
     pl = torch.empty((Hq, P), dtype=torch.float32, device=query_states.device)
     check(lib.deft_flatten_read_partials(ws.data_ptr(), ws_bytes, NB, P, nq, Hq, Hkv, D, po.data_ptr(), pl.data_ptr(), st),

@@ -129,17 +129,17 @@ def tree_tokens(w: Workload) -> int:
     raise ValueError(w.kind)
 
 
-def build_tree(w: Workload, layers: int, device: str, extra_slots: int = 256, pools=None):
+def build_tree(w: Workload, layers: int, device: str, extra_slots: int = 256, pools=None, dtype=torch.float16):
     """Returns (tree, kv_pool).  The pool holds `layers` distinct per-layer KV arrays.
     `pools` = (req_pool, kv_pool) grows the tree inside existing pools (forests)."""
     Hq, Hkv, D, _ = GEOMETRY[w.model]
     if pools is None:
         size = tree_tokens(w) + extra_slots
         req = ReqToTokenPool(max(w.width, 64) + 8, size + 8, device=device)
-        pool = TokenToKVPool(size, torch.float16, Hkv, D, layers, device=device)
+        pool = TokenToKVPool(size, dtype, Hkv, D, layers, device=device)
     else:
         req, pool = pools
-    tree = TreeCache(torch.float16, Hkv, D, layers, req, pool, None, True, False)
+    tree = TreeCache(dtype, Hkv, D, layers, req, pool, None, True, False)
     tree.init_prompt(torch.arange(1, w.prefix + 1, dtype=torch.int32))
 
     def step(n):
@@ -172,7 +172,7 @@ def algorithmic_bytes(n_kv_tokens: int, nq: int, Hq: int, Hkv: int, D: int) -> i
     return 4 * n_kv_tokens * Hkv * D + 4 * nq * Hq * D
 
 
-def build_forest(w: Workload, n_trees: int, layers: int, device: str, extra_slots: int = 256):
+def build_forest(w: Workload, n_trees: int, layers: int, device: str, extra_slots: int = 256, dtype=torch.float16):
     """`n_trees` independent trees of shape `w` in ONE pool (BASELINE configs[4]: a GPU's share of the 64-tree
     batch).  Trees are built one after the other, so each tree's prompt is contiguous and its decode-step slots
     interleave across its own leaves only.  Returns (Forest, kv_pool)."""
@@ -181,12 +181,12 @@ def build_forest(w: Workload, n_trees: int, layers: int, device: str, extra_slot
     Hq, Hkv, D, _ = GEOMETRY[w.model]
     size = n_trees * tree_tokens(w) + extra_slots
     req = ReqToTokenPool(n_trees * (max(w.width, 64) + 8), tree_tokens(w) + 16, device=device)
-    pool = TokenToKVPool(size, torch.float16, Hkv, D, layers, device=device)
-    trees = [build_tree(w, layers, device, pools=(req, pool))[0] for _ in range(n_trees)]
+    pool = TokenToKVPool(size, dtype, Hkv, D, layers, device=device)
+    trees = [build_tree(w, layers, device, pools=(req, pool), dtype=dtype)[0] for _ in range(n_trees)]
     return Forest(trees), pool
 
 
-def build_forest_tree(w: Workload, n_trees: int, layers: int, device: str, extra_slots: int = 256):
+def build_forest_tree(w: Workload, n_trees: int, layers: int, device: str, extra_slots: int = 256, dtype=torch.float16):
     """The same batch as ONE tree object (`TreeCache.init_forest`: a root without tokens, the trees below it), which is what
     the device-side metadata kernels and `DecodeSession` take: per decode step only the new slot numbers cross PCIe, where
     `Forest.metadata()` rebuilds and concatenates every tree's metadata on the host.  few_shot shapes.  Returns (tree, pool)."""
@@ -194,8 +194,8 @@ def build_forest_tree(w: Workload, n_trees: int, layers: int, device: str, extra
     Hq, Hkv, D, _ = GEOMETRY[w.model]
     size = n_trees * tree_tokens(w) + extra_slots
     req = ReqToTokenPool(n_trees * (w.width + 8) + 8, tree_tokens(w) + 512, device=device)
-    pool = TokenToKVPool(size, torch.float16, Hkv, D, layers, device=device)
-    tree = TreeCache(torch.float16, Hkv, D, layers, req, pool, None, True, False)
+    pool = TokenToKVPool(size, dtype, Hkv, D, layers, device=device)
+    tree = TreeCache(dtype, Hkv, D, layers, req, pool, None, True, False)
     tree.init_forest([torch.arange(1, w.prefix + 1, dtype=torch.int32) for _ in range(n_trees)])
     for root in sorted(tree.leaves.values(), key=lambda n: n.id):
         tree.branch(root, w.width)

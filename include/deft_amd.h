@@ -26,7 +26,9 @@
  *     device memory or keeps state between calls.  The caller owns every buffer,
  *     including `workspace` (size it with the *_workspace_bytes functions).
  *   - strides are in ELEMENTS of the pointed-to type.
- *   - fp16 tensors are IEEE binary16; index tensors are int64 exactly as the
+ *   - q, the KV pool, new K/V rows and outputs are IEEE binary16 (the *_f16 entry points) or bfloat16 (their *_bf16
+ *     twins: identical parameter lists and contracts, "fp16" below reads "bfloat16" there); one element type per call;
+ *     partials, plans and workspaces do not depend on it.  Index tensors are int64 exactly as the
  *     reference's TreeMetadata holds them (tree_cache.py:813-857); cache_loc is int32
  *     (memory_pool.py:80).
  *   - KV pool layout is the reference's: per layer [slot][2][Hkv][D] fp16
@@ -129,6 +131,15 @@ int deft_flatten_decode_f16(
     const int64_t* block_bitmasks, const int64_t* block_kv, const int64_t* block_lens,
     int NB, int P, int nq, int Hq, int Hkv, int D, float scale,
     const void* plan, void* workspace, size_t workspace_bytes, void* stream);
+/* bfloat16 twin of deft_flatten_decode_f16: the same contract with bfloat16 elements */
+int deft_flatten_decode_bf16(
+    const void* q, int64_t q_stride_tok, int64_t q_stride_head,
+    const void* k_base, const void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head,
+    void* out, int64_t o_stride_tok, int64_t o_stride_head,
+    const int64_t* block_q, const int64_t* block_q_cnts, const int64_t* block_q_offset,
+    const int64_t* block_bitmasks, const int64_t* block_kv, const int64_t* block_lens,
+    int NB, int P, int nq, int Hq, int Hkv, int D, float scale,
+    const void* plan, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
  * DeFTAttention.deft_flatten_forward in one call (deft_attention.py:110-151): the paged append of
@@ -138,6 +149,16 @@ int deft_flatten_decode_f16(
  * `plan` may be NULL (built per call) or a plan built with the same cache_loc arguments.
  */
 int deft_flatten_decode_append_f16(
+    const void* q, int64_t q_stride_tok, int64_t q_stride_head,
+    void* k_base, void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head,
+    void* out, int64_t o_stride_tok, int64_t o_stride_head,
+    const int64_t* block_q, const int64_t* block_q_cnts, const int64_t* block_q_offset,
+    const int64_t* block_bitmasks, const int64_t* block_kv, const int64_t* block_lens,
+    int NB, int P, int nq, int Hq, int Hkv, int D, float scale,
+    const int32_t* cache_loc, const void* k_new, const void* v_new, int64_t new_stride_tok, int n_new,
+    const void* plan, void* workspace, size_t workspace_bytes, void* stream);
+/* bfloat16 twin of deft_flatten_decode_append_f16: the same contract with bfloat16 elements */
+int deft_flatten_decode_append_bf16(
     const void* q, int64_t q_stride_tok, int64_t q_stride_head,
     void* k_base, void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head,
     void* out, int64_t o_stride_tok, int64_t o_stride_head,
@@ -187,12 +208,31 @@ int deft_node_decode_f16(
     const int64_t* node_q, const int64_t* node_q_offset, const int64_t* node_q_len,
     int NE, int P, int64_t total_kv, int nq, int Hq, int Hkv, int D, float scale,
     const void* plan, void* workspace, size_t workspace_bytes, void* stream);
+/* bfloat16 twin of deft_node_decode_f16: the same contract with bfloat16 elements */
+int deft_node_decode_bf16(
+    const void* q, int64_t q_stride_tok, int64_t q_stride_head,
+    const void* k_base, const void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head,
+    void* out, int64_t o_stride_tok, int64_t o_stride_head,
+    const int64_t* node_kv, const int64_t* node_kv_offset, const int64_t* node_kv_len,
+    const int64_t* node_q, const int64_t* node_q_offset, const int64_t* node_q_len,
+    int NE, int P, int64_t total_kv, int nq, int Hq, int Hkv, int D, float scale,
+    const void* plan, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
  * DeFTAttention.deft_node_forward in one call (deft_attention.py:72-108): the paged append of this step's K/V rows
  * fused into the Node attention launch; same contract as deft_flatten_decode_append_f16.
  */
 int deft_node_decode_append_f16(
+    const void* q, int64_t q_stride_tok, int64_t q_stride_head,
+    void* k_base, void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head,
+    void* out, int64_t o_stride_tok, int64_t o_stride_head,
+    const int64_t* node_kv, const int64_t* node_kv_offset, const int64_t* node_kv_len,
+    const int64_t* node_q, const int64_t* node_q_offset, const int64_t* node_q_len,
+    int NE, int P, int64_t total_kv, int nq, int Hq, int Hkv, int D, float scale,
+    const int32_t* cache_loc, const void* k_new, const void* v_new, int64_t new_stride_tok, int n_new,
+    const void* plan, void* workspace, size_t workspace_bytes, void* stream);
+/* bfloat16 twin of deft_node_decode_append_f16: the same contract with bfloat16 elements */
+int deft_node_decode_append_bf16(
     const void* q, int64_t q_stride_tok, int64_t q_stride_head,
     void* k_base, void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head,
     void* out, int64_t o_stride_tok, int64_t o_stride_head,
@@ -224,9 +264,27 @@ int deft_flatten_decode_rope_append_f16(
     const int32_t* cache_loc, const void* k_new, const void* v_new, int64_t new_stride_tok, int n_new,
     const float* cos_sin_rows, int rotary_dim, int is_neox_style,
     const void* plan, void* workspace, size_t workspace_bytes, void* stream);
+/* bfloat16 twin of deft_flatten_decode_rope_append_f16: the same contract with bfloat16 elements */
+int deft_flatten_decode_rope_append_bf16(
+    const void* q, int64_t q_stride_tok, int64_t q_stride_head, void* k_base, void* v_base, int64_t kv_stride_slot,
+    int64_t kv_stride_head, void* out, int64_t o_stride_tok, int64_t o_stride_head,
+    const int64_t* block_q, const int64_t* block_q_cnts, const int64_t* block_q_offset, const int64_t* block_bitmasks,
+    const int64_t* block_kv, const int64_t* block_lens, int NB, int P, int nq, int Hq, int Hkv, int D, float scale,
+    const int32_t* cache_loc, const void* k_new, const void* v_new, int64_t new_stride_tok, int n_new,
+    const float* cos_sin_rows, int rotary_dim, int is_neox_style,
+    const void* plan, void* workspace, size_t workspace_bytes, void* stream);
 int deft_rope_gather_rows(const int64_t* positions, const float* cos_sin_cache, int64_t cache_stride, int n, int rotary_dim,
                           float* rows_out, void* stream);
 int deft_node_decode_rope_append_f16(
+    const void* q, int64_t q_stride_tok, int64_t q_stride_head, void* k_base, void* v_base, int64_t kv_stride_slot,
+    int64_t kv_stride_head, void* out, int64_t o_stride_tok, int64_t o_stride_head,
+    const int64_t* node_kv, const int64_t* node_kv_offset, const int64_t* node_kv_len, const int64_t* node_q,
+    const int64_t* node_q_offset, const int64_t* node_q_len, int NE, int P, int64_t total_kv, int nq, int Hq, int Hkv, int D,
+    float scale, const int32_t* cache_loc, const void* k_new, const void* v_new, int64_t new_stride_tok, int n_new,
+    const float* cos_sin_rows, int rotary_dim, int is_neox_style,
+    const void* plan, void* workspace, size_t workspace_bytes, void* stream);
+/* bfloat16 twin of deft_node_decode_rope_append_f16: the same contract with bfloat16 elements */
+int deft_node_decode_rope_append_bf16(
     const void* q, int64_t q_stride_tok, int64_t q_stride_head, void* k_base, void* v_base, int64_t kv_stride_slot,
     int64_t kv_stride_head, void* out, int64_t o_stride_tok, int64_t o_stride_head,
     const int64_t* node_kv, const int64_t* node_kv_offset, const int64_t* node_kv_len, const int64_t* node_q,
@@ -249,6 +307,13 @@ int deft_prefill_f16(const void* q, int64_t q_stride_tok, int64_t q_stride_head,
                      void* out, int64_t o_stride_tok, int64_t o_stride_head,
                      const int32_t* b_start_loc, const int32_t* b_seq_len, int batch, int max_input_len,
                      int Hq, int Hkv, int D, float scale, void* stream);
+/* bfloat16 twin of deft_prefill_f16: the same contract with bfloat16 elements */
+int deft_prefill_bf16(const void* q, int64_t q_stride_tok, int64_t q_stride_head,
+                      const void* k, int64_t k_stride_tok, int64_t k_stride_head,
+                      const void* v, int64_t v_stride_tok, int64_t v_stride_head,
+                      void* out, int64_t o_stride_tok, int64_t o_stride_head,
+                      const int32_t* b_start_loc, const int32_t* b_seq_len, int batch, int max_input_len,
+                      int Hq, int Hkv, int D, float scale, void* stream);
 
 /* ---- rotary position embedding of this step's q / k rows (the op in front of the path) -----------------
  *
@@ -262,6 +327,11 @@ int deft_rope_qk_f16(void* q, int64_t q_stride_tok, int64_t q_stride_head, int H
                      void* k, int64_t k_stride_tok, int64_t k_stride_head, int Hk,
                      const int64_t* positions, const float* cos_sin_cache, int64_t cache_stride,
                      int n, int D, int rotary_dim, int is_neox_style, void* stream);
+/* bfloat16 twin of deft_rope_qk_f16: the same contract with bfloat16 elements */
+int deft_rope_qk_bf16(void* q, int64_t q_stride_tok, int64_t q_stride_head, int Hq,
+                      void* k, int64_t k_stride_tok, int64_t k_stride_head, int Hk,
+                      const int64_t* positions, const float* cos_sin_cache, int64_t cache_stride,
+                      int n, int D, int rotary_dim, int is_neox_style, void* stream);
 
 /* ---- sequential (per-request) paged attention: the reference's comparator ---------------------------------
  *
@@ -286,8 +356,23 @@ int deft_seq_decode_f16(
     void* out, int64_t o_stride_tok, int64_t o_stride_head,
     const void* plan, int nq, int64_t total_tokens, int Hq, int Hkv, int D, float scale,
     void* workspace, size_t workspace_bytes, void* stream);
+/* bfloat16 twin of deft_seq_decode_f16: the same contract with bfloat16 elements */
+int deft_seq_decode_bf16(
+    const void* q, int64_t q_stride_tok, int64_t q_stride_head,
+    const void* k_base, const void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head,
+    void* out, int64_t o_stride_tok, int64_t o_stride_head,
+    const void* plan, int nq, int64_t total_tokens, int Hq, int Hkv, int D, float scale,
+    void* workspace, size_t workspace_bytes, void* stream);
 /* store_kv_cache + token_attention_fwd in one call (radix_attention_forward, deft_attention.py:153-188) */
 int deft_seq_decode_append_f16(
+    const void* q, int64_t q_stride_tok, int64_t q_stride_head,
+    void* k_base, void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head,
+    void* out, int64_t o_stride_tok, int64_t o_stride_head,
+    const void* plan, int nq, int64_t total_tokens, int Hq, int Hkv, int D, float scale,
+    const int32_t* cache_loc, const void* k_new, const void* v_new, int64_t new_stride_tok, int n_new,
+    void* workspace, size_t workspace_bytes, void* stream);
+/* bfloat16 twin of deft_seq_decode_append_f16: the same contract with bfloat16 elements */
+int deft_seq_decode_append_bf16(
     const void* q, int64_t q_stride_tok, int64_t q_stride_head,
     void* k_base, void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head,
     void* out, int64_t o_stride_tok, int64_t o_stride_head,
@@ -300,6 +385,11 @@ int deft_seq_decode_append_f16(
 /* k_base[cache_loc[i]] = k_new[i], v_base[cache_loc[i]] = v_new[i] for i < n
  * (rows of Hkv*D fp16; new rows have token stride new_stride_tok and head stride D). */
 int deft_kv_append_f16(
+    void* k_base, void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head,
+    const int32_t* cache_loc, const void* k_new, const void* v_new, int64_t new_stride_tok,
+    int n, int Hkv, int D, void* stream);
+/* bfloat16 twin of deft_kv_append_f16: the same contract with bfloat16 elements */
+int deft_kv_append_bf16(
     void* k_base, void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head,
     const int32_t* cache_loc, const void* k_new, const void* v_new, int64_t new_stride_tok,
     int n, int Hkv, int D, void* stream);
@@ -316,6 +406,14 @@ int deft_probe_stream_read(const void* base, size_t bytes, int workgroups, void*
  * (same layout deft_flatten_decode_f16 uses).  For roofline timing of the dominant
  * kernel in isolation. */
 int deft_flatten_stage1_f16(
+    const void* q, int64_t q_stride_tok, int64_t q_stride_head,
+    const void* k_base, const void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head,
+    const int64_t* block_q, const int64_t* block_q_cnts, const int64_t* block_q_offset,
+    const int64_t* block_bitmasks, const int64_t* block_kv, const int64_t* block_lens,
+    int NB, int P, int nq, int Hq, int Hkv, int D, float scale,
+    const void* plan, void* workspace, size_t workspace_bytes, void* stream);
+/* bfloat16 twin of deft_flatten_stage1_f16: the same contract with bfloat16 elements */
+int deft_flatten_stage1_bf16(
     const void* q, int64_t q_stride_tok, int64_t q_stride_head,
     const void* k_base, const void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head,
     const int64_t* block_q, const int64_t* block_q_cnts, const int64_t* block_q_offset,

@@ -4,12 +4,19 @@ and branches between runs of decode steps; deft_amd.DecodeSession (hipGraphs per
 (tree.alloc + TreeMetadata.from_tree_cache + DeFTAttention) at every step: pool bytes and page tables bit for bit; outputs BIT FOR
 BIT for legacy sessions (incremental=False), within 1e-3 + 2^-10 |ref| (one fp16 step of the value: both sides are ROUNDED results) for window-plan sessions (incremental=True, csrc/window.h:
 the same keys in another partition).
-   tools/fuzz_session.py [seconds] [seed] [incremental: 0 | 1 | mix (default)]"""
+   tools/fuzz_session.py [seconds] [seed] [incremental: 0 | 1 | mix (default)] [--bf16]
+--bf16 (anywhere on the command line): pools, q / k / v and outputs in bfloat16.  Legacy sessions stay bit for bit; a window-plan
+session and the eager path are then each held against dense fp64 truth of the step with the a-priori bound of the bf16 kernels
+(tools/error_bound.py: u A + 2 u |o| + 2e-5 per element, u = 2^-8) -- a flat 1e-3 is below bf16's own rounding."""
 import os, sys, time, random
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
 import deft_amd
+from error_bound import bound_bf16, dense_attention  # (tools/error_bound.py: the script's own directory)
 
+BF16 = "--bf16" in sys.argv
+sys.argv = [a for a in sys.argv if a != "--bf16"]
+DTYPE = torch.bfloat16 if BF16 else torch.float16
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
 rng = random.Random(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
 inc_arg = sys.argv[3] if len(sys.argv) > 3 else "mix"
@@ -19,8 +26,24 @@ kinds = {"upload": 0, "legacy": 0, "replan": 0, "patch": 0}
 worst = 0.0
 
 
-def agree(out, ref, inc, tag):
+def step_truth(tree, md, pool, ql, l, n):
+    """bf16 runs: (fp64 truth, A) of layer l's step that has just been launched on `tree` / `pool` (its new rows are in the pool)."""
+    paths = [None] * n
+    for leaf_id, qi in md.leaf_to_q.items():
+        paths[qi] = tree.leaf_path_slots(tree.leaves[leaf_id])
+    return dense_attention(ql[:n], pool.get_key_buffer(l), pool.get_value_buffer(l), paths, Hq, Hkv, D ** -0.5, torch.float64, with_abs=True)
+
+
+def agree(out, ref, inc, tag, truth=None):
     global worst
+    if inc and BF16:
+        o, A = truth
+        tol = bound_bf16(o, A)
+        for side, t in (("session", out), ("eager", ref)):
+            err = (t.reshape(o.shape).double() - o).abs()
+            worst = max(worst, float((err / tol).max()) if err.numel() else 0.0)
+            assert bool((err <= tol).all()), (tag, side, float((err / tol).max()))
+        return
     if not inc:
         if not torch.equal(out, ref) and os.environ.get("FUZZ_VERBOSE"):
             e = (out.float() - ref.float()).abs()
@@ -49,7 +72,7 @@ while time.time() < t_end:
     smode = "node" if mode == "node_chunk" else mode
     size = 1 << 17 if Hkv <= 8 else 1 << 16
     g = torch.Generator(device="cuda").manual_seed(rng.randint(0, 10 ** 6))
-    kv_init = torch.randn((layers, size, 2, Hkv, D), dtype=torch.float16, device="cuda", generator=g)
+    kv_init = torch.randn((layers, size, 2, Hkv, D), dtype=DTYPE, device="cuda", generator=g)
     forest = rng.random() < 0.3
     prompts = [rng.choice([1, 5, 127, 128, 129, 300, 1000, 3000]) for _ in range(rng.randint(2, 4) if forest else 1)]
     widths = [rng.randint(1, 5) for _ in range(rng.randint(1, 3))]
@@ -57,8 +80,8 @@ while time.time() < t_end:
     trees = []
     for _ in range(2):
         req = deft_amd.ReqToTokenPool(512, 8192, device="cuda")
-        pool = deft_amd.TokenToKVPool(size, torch.float16, Hkv, D, layers, device="cuda")
-        tree = deft_amd.TreeCache(torch.float16, Hkv, D, layers, req, pool, None, True, False)
+        pool = deft_amd.TokenToKVPool(size, DTYPE, Hkv, D, layers, device="cuda")
+        tree = deft_amd.TreeCache(DTYPE, Hkv, D, layers, req, pool, None, True, False)
         if forest:
             tree.init_forest([torch.arange(n, dtype=torch.int32) for n in prompts])
         else:
@@ -67,9 +90,9 @@ while time.time() < t_end:
         trees.append((tree, pool))
     (te, pe), (ts, ps) = trees
     cap = 512
-    q = torch.randn((layers, cap, Hq * D), dtype=torch.float16, device="cuda", generator=g)
-    k = torch.randn((layers, cap, Hkv * D), dtype=torch.float16, device="cuda", generator=g)
-    v = torch.randn((layers, cap, Hkv * D), dtype=torch.float16, device="cuda", generator=g)
+    q = torch.randn((layers, cap, Hq * D), dtype=DTYPE, device="cuda", generator=g)
+    k = torch.randn((layers, cap, Hkv * D), dtype=DTYPE, device="cuda", generator=g)
+    v = torch.randn((layers, cap, Hkv * D), dtype=DTYPE, device="cuda", generator=g)
     nq_now = [1]
     inc = {"0": False, "1": True}.get(inc_arg, rng.random() < 0.6)
     # (round 6: other max_q_len than the default 32 now and then -- query chunks of 1 / 7 / 16 rows (not more than 32: the operators' query tile, as the reference's BLOCK_M): the reference's knob,
@@ -90,7 +113,7 @@ while time.time() < t_end:
         # step t+1 head (its own stream) overlaps step t's layers -- the outputs of every step are cloned in stream order and
         # compared at the end of the run, pool bytes and page tables then too.
         if nsteps > 1 and rng.random() < 0.5:
-            refs, outs, n = [], [], 0
+            refs, outs, truths, n = [], [], [], 0
             for _ in range(nsteps):
                 for leaf in te.leaves.values():
                     leaf.append_token(7)
@@ -99,6 +122,7 @@ while time.time() < t_end:
                 deft_amd.register_tree_metadata(md)
                 n = md.query_num
                 refs.append([attn[l](q[l, :n], k[l, :n], v[l, :n], deft_amd.InputMetadata(fmode, upd, pe)).clone() for l in range(layers)])
+                truths.append([step_truth(te, md, pe, q[l], l, n) for l in range(layers)] if inc and BF16 else [None] * layers)
             torch.cuda.synchronize()
             nq_now[0] = n
             for _ in range(nsteps):
@@ -109,7 +133,7 @@ while time.time() < t_end:
             torch.cuda.synchronize()
             for i in range(nsteps):
                 for l in range(layers):
-                    agree(outs[i][l], refs[i][l], inc, ("lagged", runs, steps + i, l, mode, Hq, Hkv, prompts, widths, lens))
+                    agree(outs[i][l], refs[i][l], inc, ("lagged", runs, steps + i, l, mode, Hq, Hkv, prompts, widths, lens), truths[i][l])
             assert torch.equal(pe._storage, ps._storage), ("lagged", runs, steps)
             assert torch.equal(te.req_to_token_pool.req_to_token, ts.req_to_token_pool.req_to_token), ("lagged", runs, steps)
             steps += nsteps
@@ -127,7 +151,8 @@ while time.time() < t_end:
             out = sess.step()
             torch.cuda.synchronize()
             for l in range(layers):
-                agree(out[l][:n], ref[l], inc, (runs, steps, l, mode, Hq, Hkv, prompts, widths, lens))
+                agree(out[l][:n], ref[l], inc, (runs, steps, l, mode, Hq, Hkv, prompts, widths, lens),
+                      step_truth(te, md, pe, q[l], l, n) if inc and BF16 else None)
             assert torch.equal(pe._storage, ps._storage), (runs, steps)
             assert torch.equal(te.req_to_token_pool.req_to_token, ts.req_to_token_pool.req_to_token), (runs, steps)
             steps += 1
@@ -179,5 +204,10 @@ while time.time() < t_end:
     deft_amd.unregister_tree_metadata()
     deft_amd.BLOCK_CONFIG["MAX_BLOCK_LEN"] = -1
     runs += 1
+if BF16:
+    print(f"session fuzz bf16 ok: {runs} trees ({sd_runs} with speculative-decoding merge / reset steps, {inc_runs} on window plans), {steps} steps "
+          f"(legacy sessions equal to the eager path bit for bit; window plans and eager path within the a-priori bound of fp64 truth, worst "
+          f"err / bound {worst:.3f}), {captures} graph captures, step kinds {kinds}")
+    sys.exit(0)
 print(f"session fuzz ok: {runs} trees ({sd_runs} with speculative-decoding merge / reset steps, {inc_runs} on window plans), {steps} steps "
       f"equal to the eager path (legacy sessions bit for bit; window plans worst |err| {worst:.2e}), {captures} graph captures, step kinds {kinds}")
