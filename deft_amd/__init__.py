@@ -17,6 +17,7 @@ from .token_attention import token_attention_fwd  # noqa: F401
 from .tree_attention import kv_append, tree_attention_fwd, tree_attention_subtree_fwd  # noqa: F401
 from .tree_cache import (  # noqa: F401
     BLOCK_CONFIG,
+    ExtendStep,
     KVCacheUpdater,
     TreeCache,
     TreeMetadata,

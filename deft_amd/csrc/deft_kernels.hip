@@ -330,6 +330,8 @@ __global__ __launch_bounds__(256, 2) void stage1_kernel(Stage1Params p) {
 #include "plan_records.h"
 #include "plan_kernels.h"
 #include "tree_plan.h"
+#define DEFT_EXTEND_KERNELS
+#include "extend.h"
 #include "window.h"
 #include "merge.h"
 #include "stage1_np.h"
@@ -2195,6 +2197,51 @@ int deft_tree_dev_build_md(int n_nodes, int nq, int nqw, const int32_t* node_sta
                                   max_block_len, nbp_cap, scratch, scratch_bytes, node_q, node_kv, node_q_len, node_kv_len,
                                   node_q_offset, node_kv_offset, block_q, block_q_cnts, block_q_offset, block_bitmasks, block_kv,
                                   block_lens, advance_loc, nullptr, PageWrite{nullptr, 0, nullptr, nullptr}, stream);
+}
+
+/* ---- EXTEND steps: several new tokens per leaf in one attention call (extend.h) ------------------------------------------- */
+size_t deft_extend_scratch_bytes(int nq, int NB_tree) {
+    if (nq < 0 || NB_tree < 0) return 0;
+    size_t bytes = 0;
+    ext_scratch_view(nullptr, nq, NB_tree, &bytes);
+    return bytes;
+}
+
+int deft_extend_dev_build(const int64_t* t_block_q, const int64_t* t_block_q_cnts, const int64_t* t_block_q_offset,
+                          const int64_t* t_block_bitmasks, const int64_t* t_block_kv, const int64_t* t_block_lens, int NB_tree,
+                          int nq, const int32_t* row_leaf, const int32_t* parent, const int32_t* cache_loc, int n_rows,
+                          int max_q_len, int NB, int P, void* scratch, size_t scratch_bytes, int64_t* block_q,
+                          int64_t* block_q_cnts, int64_t* block_q_offset, int64_t* block_bitmasks, int64_t* block_kv,
+                          int64_t* block_lens, void* stream) {
+    if (NB_tree < 0 || NB_tree > EXT_MAX_TBLOCKS || nq < 1 || n_rows < 1 || n_rows > EXT_MAX_ROWS || max_q_len < 1 || max_q_len > 32 ||
+        NB < 1 || P < 1 || !row_leaf || !parent || !cache_loc || !scratch || !block_q || !block_q_cnts || !block_q_offset ||
+        !block_bitmasks || !block_kv || !block_lens ||
+        (NB_tree > 0 && (!t_block_q || !t_block_q_cnts || !t_block_q_offset || !t_block_bitmasks || !t_block_kv || !t_block_lens))) {
+        set_error("deft_extend_dev_build: bad arguments (rows=%d of 1..%d, max_q_len=%d of 1..32, tree blocks=%d, nq=%d)", n_rows,
+                  EXT_MAX_ROWS, max_q_len, NB_tree, nq);
+        return DEFT_EINVAL;
+    }
+    size_t need = 0;
+    const ExtScratch sc = ext_scratch_view(scratch, nq, NB_tree, &need);
+    if (scratch_bytes < need) {
+        set_error("extend scratch too small: %zu < %zu", scratch_bytes, need);
+        return DEFT_EWORKSPACE;
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const ExtBlocks T{const_cast<int64_t*>(t_block_q), const_cast<int64_t*>(t_block_q_cnts), const_cast<int64_t*>(t_block_q_offset),
+                      const_cast<int64_t*>(t_block_bitmasks), const_cast<int64_t*>(t_block_kv), const_cast<int64_t*>(t_block_lens)};
+    const ExtBlocks o{block_q, block_q_cnts, block_q_offset, block_bitmasks, block_kv, block_lens};
+    const ExtStep step{row_leaf, parent, cache_loc, n_rows, nq};
+    hipLaunchKernelGGL(extend_scan_kernel, dim3(1), dim3(1024), 0, st, T, NB_tree, step, sc, max_q_len);
+    int rc = check_launch("extend scan launch");
+    if (rc) return rc;
+    if (NB_tree > 0) {
+        hipLaunchKernelGGL(extend_blocks_kernel, dim3((unsigned)NB_tree), dim3(128), 0, st, T, NB_tree, step, sc, o, max_q_len, NB, P);
+        rc = check_launch("extend blocks launch");
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(extend_new_kernel, dim3(1), dim3(1024), 0, st, step, sc, o, max_q_len, NB, P);
+    return check_launch("extend new-keys launch");
 }
 
 // deft_tree_dev_build_md with the journal replay (deft_tree_dev_apply_ops) folded into its first kernel, in front of the

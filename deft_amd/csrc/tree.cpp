@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "common.h"
+#include "extend.h"
 
 namespace deft {
 
@@ -846,6 +847,150 @@ int deft_tree_md_caps(int64_t tree, int max_q_len, int block_len, int max_block_
     sizes[6] = P;
     sizes[7] = NB * block_len;
     sizes[8] = NBp;
+    return DEFT_OK;
+}
+
+// Sizes of the Flatten arrays of an EXTEND step (extend.h) over the tree as it stands: n_rows new tokens, token t on the leaf
+// that is query row row_leaf[t] (ascending), hanging off parent[t] (-1, or an earlier row of the same leaf).
+//   sizes = {rows, NB, P, NB of the cached part, P of the cached part, NB and P of the tree's own block arrays (what
+//            deft_tree_dev_build_md writes without advance: the input of deft_extend_dev_build), physical 128-slot blocks,
+//            slots of the tree}
+// Unlike deft_tree_md_sizes it takes a leaf that holds no slot of its own yet (a fresh branch is what a step extends).
+int deft_tree_extend_sizes(int64_t tree, int max_q_len, int block_len, int n_rows, const int32_t* row_leaf, const int32_t* parent,
+                           int64_t sizes[9]) {
+    DEFT_TREE_OR_FAIL(t, tree, "deft_tree_extend_sizes");
+    const Layout& L = t->lay;
+    if (!L.valid || !sizes || !row_leaf || !parent || max_q_len < 1 || max_q_len > 32 || block_len != EXT_TILE) {
+        set_error("deft_tree_extend_sizes: no valid layout or bad arguments (max_q_len 1..32, block_len 128)");
+        return DEFT_EINVAL;
+    }
+    const int nq = (int)t->leaves.size();
+    if (n_rows < 1 || n_rows > EXT_MAX_ROWS) {
+        set_error("deft_tree_extend_sizes: %d rows (an extend step holds 1 .. %d)", n_rows, EXT_MAX_ROWS);
+        return DEFT_EINVAL;
+    }
+    std::vector<int> tok_off((size_t)nq + 1, 0);
+    for (int i = 0; i < n_rows; ++i) {
+        if (row_leaf[i] < 0 || row_leaf[i] >= nq || (i > 0 && row_leaf[i - 1] > row_leaf[i])) {
+            set_error("deft_tree_extend_sizes: row %d: leaf rows must be ascending and below %d", i, nq);
+            return DEFT_EINVAL;
+        }
+        ++tok_off[(size_t)row_leaf[i] + 1];
+    }
+    for (int r = 0; r < nq; ++r) tok_off[(size_t)r + 1] += tok_off[r];
+    for (int i = 0; i < n_rows; ++i)
+        if (parent[i] != -1 && (parent[i] < tok_off[row_leaf[i]] || parent[i] >= i)) {
+            set_error("deft_tree_extend_sizes: row %d: parent %d is not an earlier row of the same leaf", i, (int)parent[i]);
+            return DEFT_EINVAL;
+        }
+    const int mq = max_q_len;
+    // ---- cached part: the tree's blocks (md_sizes_for's walk), their leaf lists cut into chunks of mq, expanded ----
+    const int n = (int)L.dfs.size(), nqw = L.nqw;
+    const std::vector<uint64_t> refs = leaf_bitsets(t, L);
+    std::vector<int64_t> len(n);
+    int64_t total = 0;
+    for (int i = 0; i < n; ++i) {
+        len[i] = (int64_t)node_of(t, L.dfs[i])->kv.size();
+        total += len[i];
+    }
+    const int64_t NBp = (total + block_len - 1) / block_len;
+    int64_t NBT = 0, PT = 0, NBc = 0, Pc = 0;
+    {
+        std::vector<uint64_t> uni(nqw);
+        int i = 0;
+        int64_t pos = 0;
+        for (int64_t b = 0; b < NBp; ++b) {
+            const int64_t lo = b * block_len, hi = std::min(total, lo + block_len);
+            std::fill(uni.begin(), uni.end(), 0ull);
+            while (i < n && pos + len[i] <= lo) pos += len[i++];
+            int j = i;
+            int64_t pj = pos;
+            while (j < n && pj < hi) {
+                if (len[j] > 0)
+                    for (int w = 0; w < nqw; ++w) uni[w] |= refs[(size_t)j * nqw + w];
+                pj += len[j++];
+            }
+            int in_chunk = 0;
+            int64_t rows = 0;
+            auto close = [&]() {
+                if (in_chunk == 0) return;
+                ++NBT;
+                PT += in_chunk;
+                NBc += (rows + mq - 1) / mq;
+                Pc += rows;
+                in_chunk = 0;
+                rows = 0;
+            };
+            for (int r = 0; r < nq; ++r)
+                if ((uni[r >> 6] >> (r & 63)) & 1ull) {
+                    ++in_chunk;
+                    rows += tok_off[(size_t)r + 1] - tok_off[r];
+                    if (in_chunk == mq) close();
+                }
+            close();
+        }
+    }
+    if (NBT > EXT_MAX_TBLOCKS) {
+        set_error("deft_tree_extend_sizes: %lld blocks (an extend step takes trees of up to %d)", (long long)NBT, EXT_MAX_TBLOCKS);
+        return DEFT_EUNSUPPORTED;
+    }
+    // ---- new keys: pieces of mq rows per leaf, keys = ancestors-or-self inside the leaf, packed as extend_new_kernel does ----
+    std::vector<uint16_t> pc_rows, pc_keys, pc_row0;
+    std::vector<std::vector<uint8_t>> member;  // per piece: which tokens of the leaf are keys
+    int64_t words = 0;                         // ... and the words the device keeps that in
+    for (int i = 0; i < n_rows; ++i) {
+        const int a = tok_off[row_leaf[i]], m = tok_off[(size_t)row_leaf[i] + 1] - a;
+        if ((i - a) % mq == 0) {
+            words += extend_piece_words(m);
+            pc_row0.push_back((uint16_t)i);
+            pc_rows.push_back((uint16_t)std::min(mq, a + m - i));
+            member.emplace_back((size_t)m, (uint8_t)0);
+        }
+        for (int u = i; u >= 0; u = parent[u]) member.back()[(size_t)(u - a)] = 1;
+    }
+    if (words > EXT_MAX_WORDS) {
+        set_error("deft_tree_extend_sizes: the step's pieces need %lld bit-set words (at most %d: a leaf with M tokens takes "
+                  "ceil(M / max_q_len) * ceil(M / 64); use max_q_len >= 16 or fewer tokens per leaf)", (long long)words, EXT_MAX_WORDS);
+        return DEFT_EUNSUPPORTED;
+    }
+    const int np = (int)pc_rows.size();
+    pc_keys.resize(np);
+    std::vector<std::vector<int>> rank(np);  // key index of every member token
+    for (int p = 0; p < np; ++p) {
+        int c = 0;
+        rank[p].assign(member[p].size(), -1);
+        for (size_t d = 0; d < member[p].size(); ++d)
+            if (member[p][d]) rank[p][d] = c++;
+        pc_keys[p] = (uint16_t)c;
+    }
+    std::vector<uint16_t> blk(np), koff(np), roff(np), blk_len(EXT_MAX_NEWBLK);
+    const int NBn = extend_pack_pieces(np, pc_rows.data(), pc_keys.data(), blk.data(), koff.data(), roff.data(), blk_len.data(),
+                                       EXT_MAX_NEWBLK, mq);
+    if (NBn > EXT_MAX_NEWBLK) {
+        set_error("deft_tree_extend_sizes: %d new-key blocks (at most %d)", NBn, EXT_MAX_NEWBLK);
+        return DEFT_EUNSUPPORTED;
+    }
+    // a block lists the rows that see one of its slots
+    std::vector<uint32_t> row_mask((size_t)NBn, 0u);
+    for (int p = 0; p < np; ++p) {
+        const int a = tok_off[row_leaf[pc_row0[p]]];
+        for (int i = pc_row0[p]; i < pc_row0[p] + pc_rows[p]; ++i)
+            for (int u = i; u >= 0; u = parent[u]) {
+                const int b = blk[p] + (pc_keys[p] > EXT_TILE ? rank[p][(size_t)(u - a)] >> 7 : 0);
+                row_mask[(size_t)b] |= 1u << (roff[p] + (i - pc_row0[p]));
+            }
+    }
+    int64_t Pn = 0;
+    for (uint32_t m : row_mask) Pn += __builtin_popcount(m);
+    sizes[0] = n_rows;
+    sizes[1] = NBc + NBn;
+    sizes[2] = Pc + Pn;
+    sizes[3] = NBc;
+    sizes[4] = Pc;
+    sizes[5] = NBT;
+    sizes[6] = PT;
+    sizes[7] = NBp;
+    sizes[8] = total;
     return DEFT_OK;
 }
 

@@ -202,6 +202,9 @@ class DeFTAttention(nn.Module):
                           input_metadata: InputMetadata) -> torch.Tensor:
         md = get_global_tree_metadata()
         assert md is not None
+        if getattr(md, "extend_step", None) is not None:
+            raise DeftLibraryError("the registered TreeMetadata is an extend step's (TreeMetadata.for_extend): it has no Node arrays; "
+                                   "run it with ForwardMode.EXTEND")
         _check_query_tile(md)
         assert input_metadata.token_to_kv_pool is not None
         step = _decode_step(ForwardMode.TREE_DECODE_NODE, md, input_metadata, q, k, self.tp_q_head_num,
@@ -265,6 +268,47 @@ class DeFTAttention(nn.Module):
             o.view(-1, self.tp_q_head_num, self.head_dim),
             md.block_len, md.block_q, md.block_q_cnts, md.block_q_offset,
             md.block_bitmasks, md.block_kv, md.block_lens,
+        )
+        return o
+
+    def extend_forward(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+                       input_metadata: InputMetadata) -> torch.Tensor:
+        """Several new tokens per leaf in one call (not in the reference): row t of q / k / v is token t of the extend step whose
+        metadata is registered (`TreeMetadata.for_extend`), `input_metadata.kv_updater.cache_loc` the step's slots.  The K/V rows
+        go to the pool and every row attends over its leaf's cached path plus the step's tokens that are its ancestors or itself
+        -- the Flatten operator on the step's block arrays, the paged append fused into its launch."""
+        md = get_global_tree_metadata()
+        assert md is not None
+        ext = getattr(md, "extend_step", None)
+        if ext is None:
+            raise DeftLibraryError("ForwardMode.EXTEND needs the metadata of an extend step (TreeMetadata.for_extend) registered")
+        _check_query_tile(md)
+        pool = input_metadata.token_to_kv_pool
+        updater = input_metadata.kv_updater
+        assert pool is not None
+        if updater is None or updater.cache_loc is None or updater.token_to_kv_pool is not pool:
+            raise DeftLibraryError("ForwardMode.EXTEND needs input_metadata.kv_updater with the step's cache_loc")
+        if q.shape[0] != md.query_num or updater.cache_loc.shape[0] != md.query_num:
+            raise ValueError(f"extend step of {md.query_num} tokens, but q has {q.shape[0]} rows and cache_loc {updater.cache_loc.shape[0]}")
+        step = _decode_step(ForwardMode.TREE_DECODE_FLATTEN, md, input_metadata, q, k, self.tp_q_head_num,
+                            self.tp_k_head_num, self.head_dim)
+        if step is not None:
+            return step.run(self.layer_id, q, k, v)
+        k = k.view(-1, self.tp_k_head_num, self.head_dim)
+        v = v.view(-1, self.tp_v_head_num, self.head_dim)
+        o = torch.empty((q.shape[0], self.tp_q_head_num * self.head_dim), dtype=q.dtype, device=q.device)
+        if _fused_append_enabled():
+            flatten_append_attention(
+                q.view(-1, self.tp_q_head_num, self.head_dim), pool.kv_data[self.layer_id],
+                o.view(-1, self.tp_q_head_num, self.head_dim), updater.cache_loc, k, v,
+                md.block_len, md.block_q, md.block_q_cnts, md.block_q_offset, md.block_bitmasks, md.block_kv, md.block_lens,
+            )
+            return o
+        self.store_kv_cache(k, v, input_metadata)
+        tree_attention_subtree_fwd(
+            q.view(-1, self.tp_q_head_num, self.head_dim), pool.get_key_buffer(self.layer_id),
+            pool.get_value_buffer(self.layer_id), o.view(-1, self.tp_q_head_num, self.head_dim),
+            md.block_len, md.block_q, md.block_q_cnts, md.block_q_offset, md.block_bitmasks, md.block_kv, md.block_lens,
         )
         return o
 
@@ -360,8 +404,10 @@ class DeFTAttention(nn.Module):
             return self.deft_flatten_forward(q, k, v, input_metadata)
         if mode == ForwardMode.TREE_DECODE_NODE:
             return self.deft_node_forward(q, k, v, input_metadata)
+        if mode == ForwardMode.EXTEND:
+            return self.extend_forward(q, k, v, input_metadata)
         raise NotImplementedError(
-            f"Unsupported forward mode: {mode} (deft_amd covers TREE_DECODE_FLATTEN, TREE_DECODE_NODE, DECODE and PREFILL with paged KV)"
+            f"Unsupported forward mode: {mode} (deft_amd covers TREE_DECODE_FLATTEN, TREE_DECODE_NODE, EXTEND, DECODE and PREFILL with paged KV)"
         )
 
     def store_kv_cache(self, cache_k: torch.Tensor, cache_v: torch.Tensor, input_metadata: InputMetadata) -> None:

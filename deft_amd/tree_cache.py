@@ -280,6 +280,34 @@ class BranchSequence:
         self.token_ids.extend(tokens)
 
 
+@dataclass
+class ExtendStep:
+    """One extend step, as `TreeCache.alloc_extend` hands it out: R new tokens, several per live leaf, that one attention
+    call (`ForwardMode.EXTEND`) serves.  Token t is query row t and new K/V row t.  Rows are grouped by leaf in ascending leaf
+    id -- the metadata's query order -- and keep the order given inside a leaf.  The tree itself is unchanged until
+    `TreeCache.commit_extend`."""
+
+    cache_loc: torch.Tensor  # [R] int32, pool device: the fresh slot of every token (what KVCacheUpdater / the fused append take)
+    slots: np.ndarray        # [R] int32, the same on the host
+    row_leaf: np.ndarray     # [R] int64, id of the token's leaf
+    parents: np.ndarray      # [R] int32, -1 = hangs off the end of the leaf's cached path, else an earlier row of the same leaf
+    positions: np.ndarray    # [R] int64, leaf length + depth: the token's position for the rotary embedding
+    token_ids: List[int]
+    leaf_rows: Dict[int, range]  # leaf id -> its rows
+    is_chain: bool           # every leaf's tokens form one chain (parent = the row in front)
+    committed: bool = False
+
+    @property
+    def num_rows(self) -> int:
+        return len(self.slots)
+
+    def updater(self, pool) -> "KVCacheUpdater":
+        return KVCacheUpdater(True, pool, self.cache_loc, None, False)
+
+
+EXTEND_MAX_ROWS = 1024  # rows of one extend step (deft_amd/csrc/extend.h)
+
+
 class TreeCache:
     def __init__(
         self,
@@ -403,6 +431,127 @@ class TreeCache:
         table = self.req_to_token_pool.req_to_token
         table[self.leaf_to_req[leaf.id], start : start + n] = cache_loc.to(table.device)
         return KVCacheUpdater(True, self.token_to_kv_pool, cache_loc, None, True)
+
+    # ---- extend steps: several tokens per leaf in ONE attention call (not in the reference) ----------------------------
+    def alloc_extend(self, tokens_by_leaf, parents=None) -> ExtendStep:
+        """Slots for an extend step, from the pool only -- the tree does not change until `commit_extend`.
+        `tokens_by_leaf`: {leaf (TreeNode or id): token ids}.  `parents`: None = every leaf's tokens are one chain; a dict
+        {leaf: [index INSIDE the leaf's tokens of each token's parent, -1 = the end of the cached path]}; or one flat sequence
+        over the step's rows (ascending leaf id, given order inside a leaf) of row indices.  A parent comes before its child."""
+        items = {}
+        for leaf, toks in tokens_by_leaf.items():
+            lid = leaf.id if isinstance(leaf, TreeNode) else int(leaf)
+            if lid not in self.leaves:
+                raise ValueError(f"alloc_extend: node {lid} is not a live leaf")
+            ids = [int(x) for x in torch.as_tensor(toks).reshape(-1).tolist()]
+            if ids:
+                items[lid] = items.get(lid, []) + ids
+        R = sum(len(v) for v in items.values())
+        if R == 0:
+            raise ValueError("alloc_extend: an extend step holds at least one token")
+        if R > EXTEND_MAX_ROWS:
+            raise ValueError(f"alloc_extend: {R} tokens; an extend step holds at most {EXTEND_MAX_ROWS}")
+        order = sorted(items)
+        leaf_rows, at = {}, 0
+        for lid in order:
+            leaf_rows[lid] = range(at, at + len(items[lid]))
+            at += len(items[lid])
+        row_leaf = np.concatenate([np.full(len(items[l]), l, dtype=np.int64) for l in order])
+        par = np.empty(R, dtype=np.int32)
+        if parents is None:
+            for lid in order:
+                rows = leaf_rows[lid]
+                par[rows.start : rows.stop] = np.arange(rows.start - 1, rows.stop - 1)
+                par[rows.start] = -1
+        elif isinstance(parents, dict):
+            given = {(k.id if isinstance(k, TreeNode) else int(k)): v for k, v in parents.items()}
+            for lid in order:
+                rows = leaf_rows[lid]
+                loc = [int(x) for x in given.get(lid, range(-1, len(rows) - 1))]
+                if len(loc) != len(rows):
+                    raise ValueError(f"alloc_extend: leaf {lid} has {len(rows)} tokens and {len(loc)} parents")
+                for i, p in enumerate(loc):
+                    if p < -1 or p >= i:
+                        raise ValueError(f"alloc_extend: leaf {lid}, token {i}: parent {p} is not an earlier token of the leaf")
+                    par[rows.start + i] = -1 if p < 0 else rows.start + p
+        else:
+            flat = [int(x) for x in parents]
+            if len(flat) != R:
+                raise ValueError(f"alloc_extend: {R} tokens and {len(flat)} parents")
+            for t, p in enumerate(flat):
+                if p < -1 or p >= t:
+                    raise ValueError(f"alloc_extend: row {t}: parent {p} is not an earlier row")
+                if p >= 0 and row_leaf[p] != row_leaf[t]:
+                    raise ValueError(f"alloc_extend: row {t}: parent {p} belongs to another leaf")
+                par[t] = p
+        depth = np.zeros(R, dtype=np.int64)
+        for t in range(R):
+            depth[t] = 0 if par[t] < 0 else depth[par[t]] + 1
+        pos = np.empty(R, dtype=np.int64)
+        chain = True
+        for lid in order:
+            rows, leaf = leaf_rows[lid], self.leaves[lid]
+            pos[rows.start : rows.stop] = leaf.position_offset + len(leaf.token_ids) + depth[rows.start : rows.stop]
+            chain = chain and bool((depth[rows.start : rows.stop] == np.arange(len(rows))).all())
+        loc = self.token_to_kv_pool.alloc_host(R)
+        if loc is None:
+            raise RuntimeError(f"alloc_extend: the KV pool has no {R} free slots")
+        cache_loc = torch.from_numpy(loc).to(self.token_to_kv_pool.device)
+        return ExtendStep(cache_loc=cache_loc, slots=loc, row_leaf=row_leaf, parents=par, positions=pos,
+                          token_ids=[x for l in order for x in items[l]], leaf_rows=leaf_rows, is_chain=chain)
+
+    def commit_extend(self, step: ExtendStep, accepted=None) -> None:
+        """The step's tokens join the tree.  `accepted`: {leaf: rows of the step to keep} -- per leaf a chain that starts at a
+        row hanging off the cached path, every further row the child of the one in front; leaves it does not name keep nothing.
+        None keeps everything and is legal for chain steps only.  Kept slots join their leaf (journalled: the device copy of the
+        tree stays inside its epoch while the leaf has room), token ids, positions and page-table rows are written as
+        `extend_leaf` writes them; every other slot of the step goes back to the pool."""
+        if step.committed:
+            raise RuntimeError("commit_extend: the step was committed already")
+        if accepted is None:
+            if not step.is_chain:
+                raise ValueError("commit_extend: accepted=None keeps every token, which only a chain step allows")
+            keep = {lid: list(rows) for lid, rows in step.leaf_rows.items()}
+        else:
+            keep = {}
+            for leaf, rows in accepted.items():
+                lid = leaf.id if isinstance(leaf, TreeNode) else int(leaf)
+                if lid not in step.leaf_rows:
+                    raise ValueError(f"commit_extend: leaf {lid} has no token in the step")
+                rows = [int(r) for r in rows]
+                prev = -1
+                for r in rows:
+                    if r not in step.leaf_rows[lid] or int(step.parents[r]) != prev:
+                        raise ValueError(f"commit_extend: leaf {lid}: rows {rows} are not a chain from the cached path")
+                    prev = r
+                keep[lid] = rows
+        for lid in keep:
+            if lid not in self.leaves:
+                raise ValueError(f"commit_extend: node {lid} is not a live leaf (any more)")
+            # (everything is checked before anything is committed: positions and page-table rows were laid out for the leaf as
+            #  `alloc_extend` saw it -- the first row of a leaf hangs off the cached path, so its position is the leaf's length then)
+            leaf, at = self.leaves[lid], int(step.positions[step.leaf_rows[lid].start])
+            if leaf.position_offset + len(leaf.token_ids) != at:
+                raise RuntimeError(f"commit_extend: leaf {lid} holds {leaf.position_offset + len(leaf.token_ids)} tokens, the step "
+                                   f"was allocated behind {at}: the leaf changed between alloc_extend and commit_extend")
+        kept = np.zeros(step.num_rows, dtype=bool)
+        table = self.req_to_token_pool.req_to_token
+        for lid in sorted(keep):
+            rows = keep[lid]
+            if not rows:
+                continue
+            kept[rows] = True
+            leaf, n = self.leaves[lid], len(rows)
+            start = leaf.position_offset + len(leaf.token_ids)
+            loc = step.slots[rows]
+            loc64 = np.ascontiguousarray(loc, dtype=np.int64)
+            check(lib.deft_tree_extend_node(self._native, lid, n, _ptr(loc64)), "deft_tree_extend_node")
+            leaf.token_ids.extend(step.token_ids[r] for r in rows)
+            leaf.positions.extend(range(start, start + n))
+            table[self.leaf_to_req[lid], start : start + n] = torch.from_numpy(np.ascontiguousarray(loc)).to(table.device)
+        if not kept.all():
+            self.token_to_kv_pool.free(step.slots[~kept])
+        step.committed = True
 
     # ---- :242-259 -------------------------------------------------------------
     def new_node(self, parent: TreeNode) -> TreeNode:
@@ -699,9 +848,11 @@ class _DeviceTree:
                            # window plan re-plans when somebody else moved the copy between two of its steps
         self.stage = None  # pinned staging buffer of the upload image
         self.stage_event = None
+        self.out = None
+        self.defer_outputs = False  # set by `sync(outputs=False)` around an upload: an extend step sizes its own arrays
 
     def _upload(self) -> None:
-        t, (mq, bl, mbl) = self.tree, self.cfg
+        t = self.tree
         sizes = np.zeros(5, dtype=np.int64)
         check(lib.deft_tree_layout(t._native, self.SLACK, _ptr(sizes)), "deft_tree_layout")
         n, nq, nqw, total_cap, epoch = (int(x) for x in sizes)
@@ -730,7 +881,23 @@ class _DeviceTree:
         base = dev.data_ptr()
         self.p_start, self.p_len, self.p_cap = base, base + 4 * n, base + 8 * n
         self.p_leaf, self.p_slots, self.p_refs = base + 12 * n, base + 4 * (3 * n + nq), base + 4 * n32
-        # output buffers for the largest tree of this epoch (every leaf SLACK tokens longer)
+        if not self.defer_outputs:
+            self._size_outputs()
+        else:
+            # (an extend step sizes its own arrays, and takes trees a decode step refuses -- a leaf without a slot of its own:
+            #  the decode outputs are sized, and such a tree refused, by the first `sync()` of the epoch that asks for them)
+            self.out = None
+            sb = int(lib.deft_tree_dev_scratch_bytes(n, nqw, 0))
+            self.scratch = torch.zeros(sb, dtype=torch.uint8, device=self.device)
+            self.scratch_bytes = sb
+        # (read AFTER the fetch: a fetch that found a non-empty journal ends the epoch for every other copy -- they never saw those
+        #  changes -- and this copy, whose image holds them, adopts the new number)
+        self.epoch = t._epoch()
+
+    def _size_outputs(self) -> None:
+        """Output buffers for the largest tree of this epoch (every leaf SLACK tokens longer)."""
+        t, (mq, bl, mbl) = self.tree, self.cfg
+        n, nqw = self.n, self.nqw
         cap = np.zeros(9, dtype=np.int64)
         # (a node's room is rounded up to a multiple of four slots, so a leaf can outgrow SLACK by three)
         # (upper bounds over EVERY growth up to that: block counts and query lists are not monotone in the leaves' lengths)
@@ -741,19 +908,24 @@ class _DeviceTree:
         sb = int(lib.deft_tree_dev_scratch_bytes(n, nqw, self.nbp_cap))
         self.scratch = torch.zeros(sb, dtype=torch.uint8, device=self.device)  # (dims[] start at zero)
         self.scratch_bytes = sb
-        # (read AFTER the fetch: a fetch that found a non-empty journal ends the epoch for every other copy -- they never saw those
-        #  changes -- and this copy, whose image holds them, adopts the new number)
-        self.epoch = t._epoch()
 
-    def sync(self) -> bool:
+    def sync(self, outputs: bool = True) -> bool:
         """Bring the device copy to the tree's structural epoch; True iff an upload happened (the uploaded image holds
         every slot the native tree holds NOW; a copy that was already current holds what it held before).  Changes the epoch
         absorbed -- slots appended to a node with room, a node's slots dropped: the native tree's journal -- are replayed on a
-        copy that stays."""
-        if self.epoch != self.tree._epoch():
-            self._upload()
-            return True
-        return self.apply_journal() < 0
+        copy that stays.  `outputs=False` leaves the decode output buffers of a new epoch unsized until somebody asks for them."""
+        self.defer_outputs = not outputs
+        try:
+            if self.epoch != self.tree._epoch():
+                self._upload()
+                uploaded = True
+            else:
+                uploaded = self.apply_journal() < 0
+        finally:
+            self.defer_outputs = False
+        if outputs and self.out is None:
+            self._size_outputs()
+        return uploaded
 
     def apply_journal(self) -> int:
         """Hand the native tree's journal of absorbed changes to the device copy (eager: one small upload + one kernel); returns
@@ -809,6 +981,54 @@ class _DeviceTree:
         views.update(query_num=int(sizes[0]), node_num=int(sizes[1]), total_kv_len=int(sizes[2]),
                      leaf_to_q={int(l): i for i, l in enumerate(leaf_ids[:nl])})
         return views
+
+    def build_extend(self, step: "ExtendStep") -> Dict[str, object]:
+        """The six Flatten arrays of an extend step (deft_amd/csrc/extend.h): the tree's own block arrays are built WITHOUT
+        advance -- the tree as it stands, query rows = leaves -- and expanded on the device with the step's
+        {leaf row, parent, cache_loc}; one small upload (3 R int32), no round trip.  Fresh tensors every call."""
+        self.sync(outputs=False)
+        t, (mq, bl, mbl) = self.tree, self.cfg
+        R = step.num_rows
+        leaf_ids = np.empty(max(self.nq, 1), dtype=np.int64)
+        nl = int(lib.deft_tree_leaf_ids(t._native, _ptr(leaf_ids), len(leaf_ids)))
+        row_of = {int(l): i for i, l in enumerate(leaf_ids[:nl])}
+        up = np.empty((3, R), dtype=np.int32)
+        try:
+            up[0] = [row_of[int(l)] for l in step.row_leaf]
+        except KeyError as e:
+            raise ValueError(f"extend step names leaf {e.args[0]}, which is not a live leaf of the tree (any more)") from None
+        up[1], up[2] = step.parents, step.slots
+        sizes = np.zeros(9, dtype=np.int64)
+        check(lib.deft_tree_extend_sizes(t._native, mq, bl, R, _ptr(up[0]), _ptr(up[1]), _ptr(sizes)), "deft_tree_extend_sizes")
+        _, NB, P, _, _, NBT, PT, NBp, total = (int(x) for x in sizes)
+        dev = self.device
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        up_d = torch.from_numpy(up).to(dev)
+        # the tree's own arrays in one buffer: block_q | cnts | offset | bitmasks | kv | lens
+        tbuf = torch.empty(max(PT + 3 * NBT + 2 * NBT * bl, 1), dtype=torch.int64, device=dev)
+        tp, off = [], 0
+        for ln in (PT, NBT, NBT, NBT * bl, NBT * bl, NBT):  # (_FIELDS order of the block arrays)
+            tp.append(tbuf.data_ptr() + 8 * off)
+            off += ln
+        sb = int(lib.deft_tree_dev_scratch_bytes(self.n, self.nqw, NBp))
+        scratch = torch.zeros(sb, dtype=torch.uint8, device=dev)
+        if NBT:
+            check(lib.deft_tree_dev_build_md(*self._tree_args(), mq, bl, mbl, NBp, scratch.data_ptr(), sb, *([None] * 6), *tp, None,
+                                             stream), "deft_tree_dev_build_md")
+        esb = int(lib.deft_extend_scratch_bytes(self.nq, NBT))
+        escratch = torch.zeros(esb, dtype=torch.uint8, device=dev)
+        out = {"block_q": torch.empty(P, dtype=torch.int64, device=dev),
+               "block_q_cnts": torch.empty(NB, dtype=torch.int64, device=dev),
+               "block_q_offset": torch.empty(NB, dtype=torch.int64, device=dev),
+               "block_bitmasks": torch.empty(NB * bl, dtype=torch.int64, device=dev),
+               "block_kv": torch.empty(NB * bl, dtype=torch.int64, device=dev),
+               "block_lens": torch.empty(NB, dtype=torch.int64, device=dev)}
+        check(lib.deft_extend_dev_build(*(tp if NBT else [None] * 6), NBT, self.nq, up_d[0].data_ptr(), up_d[1].data_ptr(),
+                                        up_d[2].data_ptr(), R, mq, NB, P, escratch.data_ptr(), esb,
+                                        *[out[k].data_ptr() for k in _FIELDS[6:]], stream), "deft_extend_dev_build")
+        out.update(query_num=R, node_num=0, total_kv_len=total + R, _ext_dims=escratch[:32].view(torch.int32),
+                   _ext_sizes=sizes, _keep=(up_d, tbuf, scratch))
+        return out
 
     def dims(self) -> List[int]:
         """dims[] as the device wrote them (debug / tests; synchronises)."""
@@ -908,6 +1128,39 @@ class TreeMetadata:
             leaf_to_q=host["leaf_to_q"], block_len=block_len, **views,
         )
         md.max_q_len = int(max_q_len)
+        return md
+
+
+    @classmethod
+    def for_extend(cls, tree: TreeCache, step: ExtendStep, max_q_len: int = 32, copy: bool = False) -> "TreeMetadata":
+        """Metadata of an extend step (`TreeCache.alloc_extend`): the `block_*` fields are the Flatten arrays whose query rows
+        are the step's TOKENS -- row t sees its leaf's cached path and the step's tokens that are t or an ancestor of t --
+        built on the GPU from the device copy of the tree (deft_amd/csrc/extend.h).  `query_num` = rows of the step; the Node
+        fields are empty (the Node operators refuse the object).  The tensors are fresh every call, so `copy` changes nothing."""
+        assert tree.root is not None
+        if not 1 <= int(max_q_len) <= 32:
+            raise ValueError(f"for_extend: max_q_len must be 1..32 (got {max_q_len})")
+        if step.committed:
+            raise RuntimeError("for_extend: the step was committed already (its tokens are part of the tree)")
+        block_len, max_block_len = BLOCK_CONFIG["BLOCK_LEN"], BLOCK_CONFIG["MAX_BLOCK_LEN"]
+        dev = tree.token_to_kv_pool.device
+        if dev.type != "cuda":
+            from ._lib import DeftLibraryError
+
+            raise DeftLibraryError("for_extend builds on the GPU: the KV pool must live on a CUDA (ROCm) device")
+        if not tree._consistent():
+            raise RuntimeError("tree.nodes / tree.leaves were edited behind TreeCache's back")
+        dt = tree._device_tree
+        if dt is None or dt.device != dev or dt.cfg != (int(max_q_len), int(block_len), int(max_block_len)):
+            dt = tree._device_tree = _DeviceTree(tree, dev, max_q_len, block_len, max_block_len)
+        views = dt.build_extend(step)
+        extra = {k: views.pop(k) for k in ("_ext_dims", "_ext_sizes", "_keep")}
+        empty = torch.empty(0, dtype=torch.int64, device=dev)
+        md = cls(block_len=block_len, leaf_to_q={l: r.start for l, r in step.leaf_rows.items()},
+                 **{k: empty for k in _FIELDS[:6]}, **views)
+        md.max_q_len = int(max_q_len)
+        md.extend_step = step
+        md.__dict__.update(extra)
         return md
 
 

@@ -557,6 +557,33 @@ int deft_tree_dev_build_md_ops(int n_nodes, int nq, int nqw, const int32_t* node
                                int32_t* page_table /* nullable */, int64_t page_stride, const int64_t* page_rows,
                                const int64_t* page_cols, void* stream);
 
+/* EXTEND steps: several new tokens per live leaf in ONE attention call (deft_amd/csrc/extend.h).  A step is n_rows tokens,
+ * 1 <= n_rows <= 1024; token t is query row t and new K/V row t (cache_loc[t] its fresh pool slot), belongs to the leaf that is
+ * query row row_leaf[t] of the tree as it stands (rows grouped by leaf: row_leaf ascending) and hangs off parent[t]: -1 = the end
+ * of the leaf's cached path, else an earlier row of the same leaf (parent[t] < t).  Row t attends over its leaf's path and over
+ * cache_loc[u] of every u that is t or an ancestor of t: chains are causal extend, general parents draft-tree verification.
+ * The functions only build the six Flatten arrays of such a step; deft_flatten_decode_append_* (n_new = nq = n_rows) runs it.
+ *   deft_tree_extend_sizes     host: sizes = {rows, NB, P, NB and P of the cached-key part, NB and P of the tree's own block
+ *                              arrays, physical 128-slot blocks of the tree, slots of the tree}.  Needs a layout
+ *                              (deft_tree_layout); takes leaves that hold no slot of their own yet.  DEFT_EUNSUPPORTED for a
+ *                              step the device kernels cannot hold (more than 1024 new-key blocks, or more than 2048 bit-set
+ *                              words: a leaf with M tokens takes ceil(M / max_q_len) * ceil(M / 64); never at max_q_len >= 16):
+ *                              a step this call accepts raises no error flag in deft_extend_dev_build
+ *   deft_extend_scratch_bytes  device scratch of one build; its first words are dims[] = {NB, P, NB cached, P cached, error flags
+ *                              (1 row_leaf, 2 parent, 4 capacity, 8 geometry)} as the kernels found them
+ *   deft_extend_dev_build      device: t_block_* = the tree's own block arrays (deft_tree_dev_build_md WITHOUT advance_loc, NB_tree
+ *                              blocks, built with the same max_q_len <= 32), row_leaf / parent / cache_loc = the step (device,
+ *                              int32), NB / P = the sizes of the output arrays (block_kv / block_bitmasks hold NB * 128) */
+int deft_tree_extend_sizes(int64_t tree, int max_q_len, int block_len, int n_rows, const int32_t* row_leaf, const int32_t* parent,
+                           int64_t sizes[9]);
+size_t deft_extend_scratch_bytes(int nq, int NB_tree);
+int deft_extend_dev_build(const int64_t* t_block_q, const int64_t* t_block_q_cnts, const int64_t* t_block_q_offset,
+                          const int64_t* t_block_bitmasks, const int64_t* t_block_kv, const int64_t* t_block_lens, int NB_tree,
+                          int nq, const int32_t* row_leaf, const int32_t* parent, const int32_t* cache_loc, int n_rows,
+                          int max_q_len, int NB, int P, void* scratch, size_t scratch_bytes, int64_t* block_q,
+                          int64_t* block_q_cnts, int64_t* block_q_offset, int64_t* block_bitmasks, int64_t* block_kv,
+                          int64_t* block_lens, void* stream);
+
 /* Window plans: the INCREMENTAL per-step head of a captured decode loop (deft_amd.DecodeSession; deft_amd/csrc/window.h).
  * Replaces, for most steps of a structural epoch, what the reference rebuilds whole on every decode step --
  * TreeMetadata.from_tree_cache, DeFT/deft/tree_decoding/tree_cache.py:619-881, timed at tree_generate.py:123-131.
