@@ -650,16 +650,9 @@ static int launch_stage1_d64(int D, const Stage1Params& p, int64_t tiles, hipStr
     return DEFT_EUNSUPPORTED;
 }
 
-// Optional fused paged append (deft_*_decode_append_f16): this step's new K/V rows and their pool slots.
-struct AppendArgs {
-    const e16* k_new = nullptr;
-    const e16* v_new = nullptr;
-    const int32_t* cache_loc = nullptr;
-    int64_t new_st = 0;
-    int n_new = 0;
-    // fused rotary embedding (optional, with the fused append only): cos | sin row of every new token, [n_new][D] fp32
-    const float* cos_sin = nullptr;
-};
+}  // namespace deft
+#include "call.h"  // Tensors, FlattenMd, NodeMd, AppendArgs, Scratch: one decode call, described and checked once
+namespace deft {
 
 static UnitList unit_list(const PlanView& pv) {
     UnitList ul;
@@ -753,6 +746,26 @@ static int launch_plan(const Stage1Params& p, int NB, const PlanView& pv, const 
 // KV heads laid out contiguously ([slot][K|V][Hkv][64], the reference's pool, memory_pool.py:61-66)
 static bool hd2_geometry(int D, int Hkv, int64_t kv_sh) { return D == 64 && Hkv % 2 == 0 && kv_sh == 64; }
 
+// The nine instantiations of stage1_np_kernel <T, 128, ROPE, NT, ROPE, HD2, DYN> (stage1_np.h) with the bit that records a raised
+// LDS cap and the name errors use: raise_lds and the launch both take the entry selected here.
+struct NpVariant {
+    void (*kernel)(NpParams);
+    unsigned attr;
+    const char* name;
+};
+template <class T>
+static NpVariant np_variant(bool hd2, bool rope, bool nt, bool dyn) {
+    if (hd2) return dyn  ? NpVariant{&stage1_np_kernel<T, 128, false, true, false, true, true>, ATTR_NP_HD2_DYN, "stage1_np_hd2_dyn"}
+                  : nt ? NpVariant{&stage1_np_kernel<T, 128, false, true, false, true>, ATTR_NP_HD2, "stage1_np_hd2"}
+                       : NpVariant{&stage1_np_kernel<T, 128, false, false, false, true>, ATTR_NP_HD2_T, "stage1_np_hd2_t"};
+    if (rope) return dyn  ? NpVariant{&stage1_np_kernel<T, 128, true, true, true, false, true>, ATTR_NP_ROPE_DYN, "stage1_np_rope_dyn"}
+                   : nt ? NpVariant{&stage1_np_kernel<T, 128, true, true>, ATTR_NP_ROPE, "stage1_np_rope"}
+                        : NpVariant{&stage1_np_kernel<T, 128, true, false>, ATTR_NP_ROPE_T, "stage1_np_rope_t"};
+    return dyn  ? NpVariant{&stage1_np_kernel<T, 128, false, true, false, false, true>, ATTR_NP_DYN, "stage1_np_dyn"}
+         : nt ? NpVariant{&stage1_np_kernel<T, 128, false, true>, ATTR_NP, "stage1_np"}
+              : NpVariant{&stage1_np_kernel<T, 128, false, false>, ATTR_NP_T, "stage1_np_t"};
+}
+
 template <class T>
 static int launch_stage1_np(const Stage1Params& p, int64_t unit_cap, const PlanView& pv, const AppendArgs& ap,
                             hipStream_t stream, int nq, bool reread = false, bool hd2 = false) {
@@ -778,16 +791,8 @@ static int launch_stage1_np(const Stage1Params& p, int64_t unit_cap, const PlanV
     // node to be folded by more than five passes.  The rest (a 64k-token prefix under 8 branches: +0.45 us of 54 with the branches
     // in) run the plain instantiation.
     const bool dyn = nt && p.G > 1 && (unit_cap * HP <= 16LL * num_cus() || (int64_t)nq * p.G > 160);
-    int rc;
-    if (hd2) rc = dyn  ? raise_lds(reinterpret_cast<const void*>(&stage1_np_kernel<T, 128, false, true, false, true, true>), SM::BYTES, attr_bit<T>(ATTR_NP_HD2_DYN), "stage1_np_hd2_dyn")
-                 : nt ? raise_lds(reinterpret_cast<const void*>(&stage1_np_kernel<T, 128, false, true, false, true>), SM::BYTES, attr_bit<T>(ATTR_NP_HD2), "stage1_np_hd2")
-                      : raise_lds(reinterpret_cast<const void*>(&stage1_np_kernel<T, 128, false, false, false, true>), SM::BYTES, attr_bit<T>(ATTR_NP_HD2_T), "stage1_np_hd2_t");
-    else if (rope) rc = dyn  ? raise_lds(reinterpret_cast<const void*>(&stage1_np_kernel<T, 128, true, true, true, false, true>), SM::BYTES, attr_bit<T>(ATTR_NP_ROPE_DYN), "stage1_np_rope_dyn")
-                       : nt ? raise_lds(reinterpret_cast<const void*>(&stage1_np_kernel<T, 128, true, true>), SM::BYTES, attr_bit<T>(ATTR_NP_ROPE), "stage1_np_rope")
-                            : raise_lds(reinterpret_cast<const void*>(&stage1_np_kernel<T, 128, true, false>), SM::BYTES, attr_bit<T>(ATTR_NP_ROPE_T), "stage1_np_rope_t");
-    else rc = dyn  ? raise_lds(reinterpret_cast<const void*>(&stage1_np_kernel<T, 128, false, true, false, false, true>), SM::BYTES, attr_bit<T>(ATTR_NP_DYN), "stage1_np_dyn")
-             : nt ? raise_lds(reinterpret_cast<const void*>(&stage1_np_kernel<T, 128, false, true>), SM::BYTES, attr_bit<T>(ATTR_NP), "stage1_np")
-                  : raise_lds(reinterpret_cast<const void*>(&stage1_np_kernel<T, 128, false, false>), SM::BYTES, attr_bit<T>(ATTR_NP_T), "stage1_np_t");
+    const NpVariant var = np_variant<T>(hd2, rope, nt, dyn);
+    const int rc = raise_lds(reinterpret_cast<const void*>(var.kernel), SM::BYTES, attr_bit<T>(var.attr), var.name);
     if (rc) return rc;
     if (unit_cap <= 0) return DEFT_OK;
     int64_t grid = unit_cap * HP;
@@ -844,16 +849,7 @@ static int launch_stage1_np(const Stage1Params& p, int64_t unit_cap, const PlanV
     npp.n_new = ap.k_new ? ap.n_new : 0;
     npp.dbg = g_dbg;
     npp.cos_sin = ap.cos_sin;
-    const dim3 g((unsigned)grid), b(256);
-    if (hd2 && dyn) hipLaunchKernelGGL((stage1_np_kernel<T, 128, false, true, false, true, true>), g, b, SM::BYTES, stream, npp);
-    else if (rope && dyn) hipLaunchKernelGGL((stage1_np_kernel<T, 128, true, true, true, false, true>), g, b, SM::BYTES, stream, npp);
-    else if (dyn) hipLaunchKernelGGL((stage1_np_kernel<T, 128, false, true, false, false, true>), g, b, SM::BYTES, stream, npp);
-    else if (hd2 && nt) hipLaunchKernelGGL((stage1_np_kernel<T, 128, false, true, false, true>), g, b, SM::BYTES, stream, npp);
-    else if (hd2) hipLaunchKernelGGL((stage1_np_kernel<T, 128, false, false, false, true>), g, b, SM::BYTES, stream, npp);
-    else if (rope && nt) hipLaunchKernelGGL((stage1_np_kernel<T, 128, true, true>), g, b, SM::BYTES, stream, npp);
-    else if (rope) hipLaunchKernelGGL((stage1_np_kernel<T, 128, true, false>), g, b, SM::BYTES, stream, npp);
-    else if (nt) hipLaunchKernelGGL((stage1_np_kernel<T, 128, false, true>), g, b, SM::BYTES, stream, npp);
-    else hipLaunchKernelGGL((stage1_np_kernel<T, 128, false, false>), g, b, SM::BYTES, stream, npp);
+    hipLaunchKernelGGL(var.kernel, dim3((unsigned)grid), dim3(256), SM::BYTES, stream, npp);
     return check_launch("stage1 np launch");
 }
 
@@ -893,33 +889,6 @@ static int launch_merge(int D, const Workspace& ws, const PlanView* pv, const in
     else DEFT_MERGE_LAUNCH(16);
 #undef DEFT_MERGE_LAUNCH
     return check_launch("merge launch");
-}
-
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-static int check_common(const void* q, int64_t q_st, int64_t q_sh, const void* k, const void* v, int64_t kv_ss,
-                        int64_t kv_sh, const void* out, int64_t o_st, int64_t o_sh, int nq, int Hq, int Hkv, int D) {
-    if (!q || !k || !v || !out) {
-        set_error("null tensor pointer");
-        return DEFT_EINVAL;
-    }
-    if (nq < 0 || Hq <= 0 || Hkv <= 0 || Hq % Hkv != 0) {
-        set_error("bad geometry nq=%d Hq=%d Hkv=%d", nq, Hq, Hkv);
-        return DEFT_EINVAL;
-    }
-    if (!deft_supported(Hq, Hkv, D)) {
-        set_error("unsupported geometry Hq=%d Hkv=%d D=%d (head_dim must be 16, 32, 64 or 128)", Hq, Hkv, D);
-        return DEFT_EUNSUPPORTED;
-    }
-    if (!aligned16(q) || !aligned16(k) || !aligned16(v) || (q_st % 8) || (q_sh % 8) || (kv_ss % 8) || (kv_sh % 8)) {
-        set_error("q/k/v rows must be 16-byte aligned (pointers and strides multiples of 8 elements)");
-        return DEFT_EINVAL;
-    }
-    if ((reinterpret_cast<uintptr_t>(out) & 3u) || (o_st % 2) || (o_sh % 2)) {
-        set_error("out rows must be 4-byte aligned");
-        return DEFT_EINVAL;
-    }
-    return DEFT_OK;
 }
 
 }  // namespace deft
@@ -990,11 +959,6 @@ size_t deft_flatten_workspace_bytes(int NB, int P, int nq, int Hq, int Hkv, int 
     return carve(nullptr, Hq, D, P, 0, plan_view(nullptr, flatten_unit_cap(NB, Hq / Hkv), P).bytes).bytes;
 }
 
-// Partial rows per tile of a Node launch: an entry has at most DEFT_MAX_Q_LEN queries -- and never more than the P (query, entry)
-// pairs of the whole call, which is what keeps the scratch of a 100k-token prefix under three branches at a tenth of the
-// 32-rows-per-tile figure.  Every sizing function and the launch derive it from P alone, so they agree.
-static inline int64_t node_rows_per_tile(int P) { return P <= 0 ? 1 : (P < DEFT_MAX_Q_LEN ? P : DEFT_MAX_Q_LEN); }
-
 size_t deft_node_workspace_bytes(int NE, int P, int64_t total_kv, int nq, int Hq, int Hkv, int D) {
     (void)nq;
     if (Hq <= 0 || Hkv <= 0 || Hq % Hkv) return 0;
@@ -1003,114 +967,61 @@ size_t deft_node_workspace_bytes(int NE, int P, int64_t total_kv, int nq, int Hq
     return carve(nullptr, Hq, D, rows, tiles, plan_view(nullptr, tiles * (Hq / Hkv), rows).bytes).bytes;
 }
 
-static int check_append(const AppendArgs& ap, int Hkv, int D) {
-    if (!ap.k_new && !ap.v_new && !ap.cache_loc) return DEFT_OK;
-    if (!ap.k_new || !ap.v_new || !ap.cache_loc || ap.n_new < 0 || (ap.new_st % 8) || ap.new_st < (int64_t)Hkv * D ||
-        !aligned16(ap.k_new) || !aligned16(ap.v_new)) {
-        set_error("bad fused-append arguments (n_new=%d new_stride=%lld)", ap.n_new, (long long)ap.new_st);
-        return DEFT_EINVAL;
-    }
-    return DEFT_OK;
-}
-
-// Fused rotary embedding (the *_rope_append_* entry points): NeoX pairing over the whole head, head_dim 128 (the
-// tile-parallel kernel), token-major q so that a virtual row's query index is its element offset / q_stride_tok.
-static int fill_rope(AppendArgs& ap, const float* cos_sin_rows, int rotary_dim, int is_neox_style, int64_t q_st,
-                     int64_t q_sh, int Hq, int D) {
-    if (!cos_sin_rows || !aligned16(cos_sin_rows)) {
-        set_error("bad fused-rope arguments (cos_sin_rows: [n_new][head_dim] fp32, 16-byte aligned)");
-        return DEFT_EINVAL;
-    }
-    if (D != 128 || rotary_dim != D || !is_neox_style) {
-        set_error("fused rope: head_dim 128, rotary_dim == head_dim, NeoX pairing (got D=%d rotary_dim=%d neox=%d); "
-                  "use deft_rope_qk_f16 + the append entry point", D, rotary_dim, is_neox_style);
-        return DEFT_EUNSUPPORTED;
-    }
-    if (q_st <= 0 || q_st > 0x7fffffffLL || (int64_t)(Hq - 1) * q_sh + D > q_st || q_sh < 0) {
-        set_error("fused rope needs token-major q (q_stride_tok=%lld q_stride_head=%lld)", (long long)q_st, (long long)q_sh);
-        return DEFT_EUNSUPPORTED;
-    }
-    ap.cos_sin = cos_sin_rows;
-    return DEFT_OK;
-}
-
 }  // extern "C"
 
 // Paged append behind both deft_kv_append_* entry points and in front of the tile-per-workgroup stage 1: one launch for either
 // element type -- the copy moves 16-byte pieces and never looks inside them.
 static int kv_append_impl(void* k_base, void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head, const int32_t* cache_loc,
                           const void* k_new, const void* v_new, int64_t new_stride_tok, int n, int Hkv, int D, void* stream);
+// head_dim 64 / 32 / 16 in the tile-per-workgroup form: the append is a launch of its own in front of stage 1
+static int append_first(const Tensors& t, const AppendArgs& ap, void* stream) {
+    if (!ap.k_new) return DEFT_OK;
+    return kv_append_impl(const_cast<void*>(t.k), const_cast<void*>(t.v), t.kv_ss, t.kv_sh, ap.cache_loc, ap.k_new, ap.v_new, ap.new_st,
+                          ap.n_new, t.Hkv, t.D, stream);
+}
 
 // Shared body of the Flatten entry points: stage 1 into the workspace; reports which
 // partial-row -> query map the merge must read.
 template <class T>
-static int flatten_stage1_impl(const void* q, int64_t q_stride_tok, int64_t q_stride_head, const void* k_base,
-                               const void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head, const int64_t* block_q,
-                               const int64_t* block_q_cnts, const int64_t* block_q_offset, const int64_t* block_bitmasks,
-                               const int64_t* block_kv, const int64_t* block_lens, int NB, int P, int nq, int Hq, int Hkv,
-                               int D, float scale, const void* plan, void* workspace, size_t workspace_bytes, void* stream,
-                               const AppendArgs& ap, Workspace* ws_out, const int32_t** row_q_out,
-                               PlanView* pv_out) {
+static int flatten_stage1_impl(const Tensors& t, const FlattenMd& md, const AppendArgs& ap, const Scratch& sc, Workspace* ws_out,
+                               const int32_t** row_q_out, PlanView* pv_out) {
     pv_out->hdr = nullptr;  // (no plan: head_dim 64)
-    // `workspace` doubles as the (unused) output pointer for the shared argument check
-    int rc = check_common(q, q_stride_tok, q_stride_head, k_base, v_base, kv_stride_slot, kv_stride_head, workspace, 2, 2,
-                          nq, Hq, Hkv, D);
+    Tensors tw = t;  // `workspace` doubles as the (unused) output pointer for the shared argument check
+    tw.out = sc.workspace;
+    tw.o_st = tw.o_sh = 2;
+    int rc = tw.check();
     if (rc) return rc;
-    if (NB < 0 || P < 0 || (NB > 0 && (!block_q || !block_q_cnts || !block_q_offset || !block_bitmasks || !block_kv ||
-                                       !block_lens))) {
-        set_error("bad Flatten metadata (NB=%d P=%d)", NB, P);
-        return DEFT_EINVAL;
-    }
-    const int64_t cap = flatten_unit_cap(NB, Hq / Hkv);
-    const Workspace ws = carve(workspace, Hq, D, P, 0, plan_view(nullptr, cap, P).bytes);
-    if (workspace_bytes < ws.bytes) {
-        set_error("workspace too small: %zu < %zu", workspace_bytes, ws.bytes);
-        return DEFT_EWORKSPACE;
-    }
+    rc = md.check();
+    if (rc) return rc;
+    const int64_t cap = md.cap(t.G());
+    const Workspace ws = carve(sc.workspace, t.Hq, t.D, md.P, 0, plan_view(nullptr, cap, md.P).bytes);
+    rc = sc.holds(ws);
+    if (rc) return rc;
     Stage1Params p{};
-    p.q = static_cast<const e16*>(q);
-    p.q_st = q_stride_tok;
-    p.q_sh = q_stride_head;
-    p.k = static_cast<const e16*>(k_base);
-    p.v = static_cast<const e16*>(v_base);
-    p.kv_ss = kv_stride_slot;
-    p.kv_sh = kv_stride_head;
-    p.block_q = block_q;
-    p.block_q_cnts = block_q_cnts;
-    p.block_q_offset = block_q_offset;
-    p.block_bitmasks = block_bitmasks;
-    p.block_kv = block_kv;
-    p.block_lens = block_lens;
+    t.fill(p);
+    md.fill(p);
     p.partial_o = ws.partial_o;
     p.partial_lse = ws.partial_lse;
     p.row_q = ws.row_q;
-    p.rows = P;
-    p.Hkv = Hkv;
-    p.G = Hq / Hkv;
-    p.scale_log2e = scale * LOG2E;
     *ws_out = ws;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const bool hd2 = hd2_geometry(D, Hkv, kv_stride_head) && !ap.cos_sin;
-    if (D == 128 || hd2) {
+    const bool hd2 = hd2_geometry(t.D, t.Hkv, t.kv_sh) && !ap.cos_sin;
+    if (t.D == 128 || hd2) {
         PlanView pv;
-        if (plan) {
-            pv = plan_view(const_cast<void*>(plan), cap, P);
+        if (sc.plan) {
+            pv = plan_view(const_cast<void*>(sc.plan), cap, md.P);
         } else {
-            pv = plan_view(ws.plan, cap, P);
-            rc = launch_plan(p, NB, pv, ap, st);
+            pv = plan_view(ws.plan, cap, md.P);
+            rc = launch_plan(p, md.NB, pv, ap, sc.st());
             if (rc) return rc;
         }
         *row_q_out = pv.row_q;
         *pv_out = pv;
-        return launch_stage1_np<T>(p, cap, pv, ap, st, nq, false, hd2);
+        return launch_stage1_np<T>(p, cap, pv, ap, sc.st(), t.nq, false, hd2);
     }
-    if (ap.k_new) {  // head_dim 64 (tile-per-workgroup form): separate append launch first
-        rc = kv_append_impl(const_cast<void*>(k_base), const_cast<void*>(v_base), kv_stride_slot, kv_stride_head,
-                                ap.cache_loc, ap.k_new, ap.v_new, ap.new_st, ap.n_new, Hkv, D, stream);
-        if (rc) return rc;
-    }
+    rc = append_first(t, ap, sc.stream);
+    if (rc) return rc;
     *row_q_out = ws.row_q;
-    return launch_stage1_d64<T, 0>(D, p, NB, st);
+    return launch_stage1_d64<T, 0>(t.D, p, md.NB, sc.st());
 }
 
 extern "C" {
@@ -1120,39 +1031,43 @@ size_t deft_flatten_plan_bytes(int NB, int P, int Hq, int Hkv) {
     return plan_view(nullptr, flatten_unit_cap(NB, Hq / Hkv), P).bytes;
 }
 
+// Shared body of the three Flatten plan builders, behind their argument checks.  `dims`: the block count of this step is read on
+// the device (below); `win`: a window plan, whose overflow blocks are laid out first (window.h).
+static int flatten_build_plan_impl(const FlattenMd& md, const Tensors& t, const AppendArgs& ap, void* plan, size_t plan_bytes,
+                                   void* stream, const int32_t* dims, const WindowArgs* win = nullptr) {
+    const PlanView pv = plan_view(plan, md.cap(t.G()), md.P);
+    int rc = plan_holds(plan_bytes, pv.bytes);
+    if (rc) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (win) {
+        // the window entry point received WRITABLE arrays: this launch appends the step's overflow blocks to them, the plan then reads them
+        auto w = [](const int64_t* a) { return const_cast<int64_t*>(a); };
+        TreeMdOut o{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, w(md.block_q), w(md.block_q_cnts), w(md.block_q_offset),
+                    w(md.block_bitmasks), w(md.block_kv), w(md.block_lens)};
+        hipLaunchKernelGGL(window_blocks_kernel, dim3(1), dim3(256), 0, st, o, win->dims, win->nq, win->max_q_len, win->win_tiles, TILE,
+                           md.NB, md.P);
+        rc = check_launch("window blocks launch");
+        if (rc) return rc;
+    }
+    Stage1Params p{};
+    t.fill(p);
+    md.fill(p);
+    return launch_plan(p, md.NB, pv, ap, st, dims, win ? win->win_tiles : 0, win ? win->win_tab : nullptr);
+}
+static int bad_plan_args(const FlattenMd& md, const Tensors& t) {
+    set_error("bad plan arguments (NB=%d P=%d Hq=%d Hkv=%d)", md.NB, md.P, t.Hq, t.Hkv);
+    return DEFT_EINVAL;
+}
+
 int deft_flatten_build_plan(const int64_t* block_q, const int64_t* block_q_cnts, const int64_t* block_q_offset,
                             const int64_t* block_bitmasks, const int64_t* block_kv, const int64_t* block_lens, int NB, int P,
                             int Hq, int Hkv, int64_t q_stride_tok, int64_t q_stride_head, int64_t kv_stride_slot,
                             const int32_t* cache_loc, int n_new, int64_t new_stride_tok, void* plan, size_t plan_bytes,
                             void* stream) {
-    if (NB < 0 || P < 0 || !plan || n_new < 0 || Hq <= 0 || Hkv <= 0 || Hq % Hkv ||
-        (NB > 0 && (!block_q || !block_q_cnts || !block_q_offset || !block_bitmasks || !block_kv || !block_lens))) {
-        set_error("bad plan arguments (NB=%d P=%d Hq=%d Hkv=%d)", NB, P, Hq, Hkv);
-        return DEFT_EINVAL;
-    }
-    const PlanView pv = plan_view(plan, flatten_unit_cap(NB, Hq / Hkv), P);
-    if (plan_bytes < pv.bytes) {
-        set_error("plan buffer too small: %zu < %zu", plan_bytes, pv.bytes);
-        return DEFT_EWORKSPACE;
-    }
-    Stage1Params p{};
-    p.block_q = block_q;
-    p.block_q_cnts = block_q_cnts;
-    p.block_q_offset = block_q_offset;
-    p.block_bitmasks = block_bitmasks;
-    p.block_kv = block_kv;
-    p.block_lens = block_lens;
-    p.rows = P;
-    p.G = Hq / Hkv;
-    p.Hkv = Hkv;
-    p.q_st = q_stride_tok;
-    p.q_sh = q_stride_head;
-    p.kv_ss = kv_stride_slot;
-    AppendArgs ap;
-    ap.cache_loc = cache_loc;
-    ap.n_new = cache_loc ? n_new : 0;
-    ap.new_st = new_stride_tok;
-    return launch_plan(p, NB, pv, ap, static_cast<hipStream_t>(stream));
+    const FlattenMd md{block_q, block_q_cnts, block_q_offset, block_bitmasks, block_kv, block_lens, NB, P};
+    const Tensors t = plan_geometry(Hq, Hkv, q_stride_tok, q_stride_head, kv_stride_slot);
+    if (!md.ok() || !plan || n_new < 0 || !t.heads_ok()) return bad_plan_args(md, t);
+    return flatten_build_plan_impl(md, t, plan_append(cache_loc, n_new, new_stride_tok), plan, plan_bytes, stream, nullptr);
 }
 
 // The same for metadata that was built ON THE DEVICE (deft_tree_dev_build_md): NB and P are the CAPACITIES of the arrays
@@ -1164,144 +1079,29 @@ int deft_flatten_build_plan_dims(const int64_t* block_q, const int64_t* block_q_
                                  const int32_t* dims, int Hq, int Hkv, int64_t q_stride_tok, int64_t q_stride_head,
                                  int64_t kv_stride_slot, const int32_t* cache_loc, int n_new, int64_t new_stride_tok, void* plan,
                                  size_t plan_bytes, void* stream) {
-    if (NB < 0 || P < 0 || !plan || !dims || n_new < 0 || Hq <= 0 || Hkv <= 0 || Hq % Hkv ||
-        (NB > 0 && (!block_q || !block_q_cnts || !block_q_offset || !block_bitmasks || !block_kv || !block_lens))) {
-        set_error("bad plan arguments (NB=%d P=%d Hq=%d Hkv=%d)", NB, P, Hq, Hkv);
-        return DEFT_EINVAL;
-    }
-    const PlanView pv = plan_view(plan, flatten_unit_cap(NB, Hq / Hkv), P);
-    if (plan_bytes < pv.bytes) {
-        set_error("plan buffer too small: %zu < %zu", plan_bytes, pv.bytes);
-        return DEFT_EWORKSPACE;
-    }
-    Stage1Params p{};
-    p.block_q = block_q;
-    p.block_q_cnts = block_q_cnts;
-    p.block_q_offset = block_q_offset;
-    p.block_bitmasks = block_bitmasks;
-    p.block_kv = block_kv;
-    p.block_lens = block_lens;
-    p.rows = P;
-    p.G = Hq / Hkv;
-    p.Hkv = Hkv;
-    p.q_st = q_stride_tok;
-    p.q_sh = q_stride_head;
-    p.kv_ss = kv_stride_slot;
-    AppendArgs ap;
-    ap.cache_loc = cache_loc;
-    ap.n_new = cache_loc ? n_new : 0;
-    ap.new_st = new_stride_tok;
-    return launch_plan(p, NB, pv, ap, static_cast<hipStream_t>(stream), dims);
+    const FlattenMd md{block_q, block_q_cnts, block_q_offset, block_bitmasks, block_kv, block_lens, NB, P};
+    const Tensors t = plan_geometry(Hq, Hkv, q_stride_tok, q_stride_head, kv_stride_slot);
+    if (!md.ok() || !plan || !dims || n_new < 0 || !t.heads_ok()) return bad_plan_args(md, t);
+    return flatten_build_plan_impl(md, t, plan_append(cache_loc, n_new, new_stride_tok), plan, plan_bytes, stream, dims);
 }
 
 }  // extern "C"
 
 template <class T>
-static int flatten_stage1_t(const void* q, int64_t q_stride_tok, int64_t q_stride_head, const void* k_base,
-                            const void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head, const int64_t* block_q,
-                            const int64_t* block_q_cnts, const int64_t* block_q_offset, const int64_t* block_bitmasks,
-                            const int64_t* block_kv, const int64_t* block_lens, int NB, int P, int nq, int Hq, int Hkv,
-                            int D, float scale, const void* plan, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!workspace) {
-        set_error("null workspace");
-        return DEFT_EINVAL;
-    }
+static int flatten_decode_impl(const Tensors& t, const FlattenMd& md, const AppendArgs& ap, const Scratch& sc) {
+    int rc = t.check();
+    if (rc) return rc;
+    rc = ap.check(t.Hkv, t.D);
+    if (rc) return rc;
+    rc = sc.check();
+    if (rc) return rc;
     Workspace ws;
     const int32_t* row_q = nullptr;
     PlanView pv;
-    return flatten_stage1_impl<T>(q, q_stride_tok, q_stride_head, k_base, v_base, kv_stride_slot, kv_stride_head, block_q,
-                               block_q_cnts, block_q_offset, block_bitmasks, block_kv, block_lens, NB, P, nq, Hq, Hkv, D,
-                               scale, plan, workspace, workspace_bytes, stream, AppendArgs(), &ws, &row_q, &pv);
-}
-
-template <class T>
-static int flatten_decode_impl(const void* q, int64_t q_stride_tok, int64_t q_stride_head, const void* k_base,
-                               const void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head, void* out,
-                               int64_t o_stride_tok, int64_t o_stride_head, const int64_t* block_q,
-                               const int64_t* block_q_cnts, const int64_t* block_q_offset, const int64_t* block_bitmasks,
-                               const int64_t* block_kv, const int64_t* block_lens, int NB, int P, int nq, int Hq, int Hkv,
-                               int D, float scale, const void* plan, void* workspace, size_t workspace_bytes, void* stream,
-                               const AppendArgs& ap) {
-    int rc = check_common(q, q_stride_tok, q_stride_head, k_base, v_base, kv_stride_slot, kv_stride_head, out,
-                          o_stride_tok, o_stride_head, nq, Hq, Hkv, D);
+    rc = flatten_stage1_impl<T>(t, md, ap, sc, &ws, &row_q, &pv);
     if (rc) return rc;
-    rc = check_append(ap, Hkv, D);
-    if (rc) return rc;
-    if (!workspace) {
-        set_error("null workspace");
-        return DEFT_EINVAL;
-    }
-    Workspace ws;
-    const int32_t* row_q = nullptr;
-    PlanView pv;
-    rc = flatten_stage1_impl<T>(q, q_stride_tok, q_stride_head, k_base, v_base, kv_stride_slot, kv_stride_head, block_q,
-                             block_q_cnts, block_q_offset, block_bitmasks, block_kv, block_lens, NB, P, nq, Hq, Hkv, D, scale,
-                             plan, workspace, workspace_bytes, stream, ap, &ws, &row_q, &pv);
-    if (rc) return rc;
-    return launch_merge<T>(D, ws, pv.hdr ? &pv : nullptr, row_q, P, out, o_stride_tok, o_stride_head, nq, Hq,
-                        (Hq / Hkv) * (hd2_geometry(D, Hkv, kv_stride_head) && !ap.cos_sin ? 2 : 1), static_cast<hipStream_t>(stream));
-}
-
-template <class T>
-static int flatten_decode_t(const void* q, int64_t q_stride_tok, int64_t q_stride_head, const void* k_base,
-                            const void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head, void* out,
-                            int64_t o_stride_tok, int64_t o_stride_head, const int64_t* block_q,
-                            const int64_t* block_q_cnts, const int64_t* block_q_offset, const int64_t* block_bitmasks,
-                            const int64_t* block_kv, const int64_t* block_lens, int NB, int P, int nq, int Hq, int Hkv,
-                            int D, float scale, const void* plan, void* workspace, size_t workspace_bytes, void* stream) {
-    return flatten_decode_impl<T>(q, q_stride_tok, q_stride_head, k_base, v_base, kv_stride_slot, kv_stride_head, out,
-                               o_stride_tok, o_stride_head, block_q, block_q_cnts, block_q_offset, block_bitmasks, block_kv,
-                               block_lens, NB, P, nq, Hq, Hkv, D, scale, plan, workspace, workspace_bytes, stream,
-                               AppendArgs());
-}
-
-template <class T>
-static int flatten_decode_append_t(const void* q, int64_t q_stride_tok, int64_t q_stride_head, void* k_base, void* v_base,
-                                   int64_t kv_stride_slot, int64_t kv_stride_head, void* out, int64_t o_stride_tok,
-                                   int64_t o_stride_head, const int64_t* block_q, const int64_t* block_q_cnts,
-                                   const int64_t* block_q_offset, const int64_t* block_bitmasks, const int64_t* block_kv,
-                                   const int64_t* block_lens, int NB, int P, int nq, int Hq, int Hkv, int D, float scale,
-                                   const int32_t* cache_loc, const void* k_new, const void* v_new, int64_t new_stride_tok,
-                                   int n_new, const void* plan, void* workspace, size_t workspace_bytes, void* stream) {
-    AppendArgs ap;
-    ap.k_new = static_cast<const e16*>(k_new);
-    ap.v_new = static_cast<const e16*>(v_new);
-    ap.cache_loc = cache_loc;
-    ap.new_st = new_stride_tok;
-    ap.n_new = n_new;
-    if (!k_new || !v_new || !cache_loc) {
-        set_error("fused append needs k_new, v_new and cache_loc");
-        return DEFT_EINVAL;
-    }
-    return flatten_decode_impl<T>(q, q_stride_tok, q_stride_head, k_base, v_base, kv_stride_slot, kv_stride_head, out,
-                               o_stride_tok, o_stride_head, block_q, block_q_cnts, block_q_offset, block_bitmasks, block_kv,
-                               block_lens, NB, P, nq, Hq, Hkv, D, scale, plan, workspace, workspace_bytes, stream, ap);
-}
-
-template <class T>
-static int flatten_decode_rope_append_t(const void* q, int64_t q_stride_tok, int64_t q_stride_head, void* k_base, void* v_base,
-                                        int64_t kv_stride_slot, int64_t kv_stride_head, void* out, int64_t o_stride_tok,
-                                        int64_t o_stride_head, const int64_t* block_q, const int64_t* block_q_cnts,
-                                        const int64_t* block_q_offset, const int64_t* block_bitmasks, const int64_t* block_kv,
-                                        const int64_t* block_lens, int NB, int P, int nq, int Hq, int Hkv, int D, float scale,
-                                        const int32_t* cache_loc, const void* k_new, const void* v_new, int64_t new_stride_tok,
-                                        int n_new, const float* cos_sin_rows, int rotary_dim, int is_neox_style,
-                                        const void* plan, void* workspace, size_t workspace_bytes, void* stream) {
-    AppendArgs ap;
-    ap.k_new = static_cast<const e16*>(k_new);
-    ap.v_new = static_cast<const e16*>(v_new);
-    ap.cache_loc = cache_loc;
-    ap.new_st = new_stride_tok;
-    ap.n_new = n_new;
-    if (!k_new || !v_new || !cache_loc) {
-        set_error("fused append needs k_new, v_new and cache_loc");
-        return DEFT_EINVAL;
-    }
-    const int rc = fill_rope(ap, cos_sin_rows, rotary_dim, is_neox_style, q_stride_tok, q_stride_head, Hq, D);
-    if (rc) return rc;
-    return flatten_decode_impl<T>(q, q_stride_tok, q_stride_head, k_base, v_base, kv_stride_slot, kv_stride_head, out,
-                               o_stride_tok, o_stride_head, block_q, block_q_cnts, block_q_offset, block_bitmasks, block_kv,
-                               block_lens, NB, P, nq, Hq, Hkv, D, scale, plan, workspace, workspace_bytes, stream, ap);
+    return launch_merge<T>(t.D, ws, pv.hdr ? &pv : nullptr, row_q, md.P, t.out, t.o_st, t.o_sh, t.nq, t.Hq,
+                        t.G() * (hd2_geometry(t.D, t.Hkv, t.kv_sh) && !ap.cos_sin ? 2 : 1), sc.st());
 }
 
 extern "C" {
@@ -1345,47 +1145,40 @@ size_t deft_node_plan_bytes(int NE, int P, int64_t total_kv, int Hq, int Hkv) {
     return plan_view(nullptr, tiles * (Hq / Hkv), tiles * node_rows_per_tile(P)).bytes;
 }
 
-static int node_build_plan_impl(const int64_t* node_kv, const int64_t* node_kv_offset, const int64_t* node_kv_len,
-                                const int64_t* node_q, const int64_t* node_q_offset, const int64_t* node_q_len, int NE, int P,
-                                int64_t total_kv, const int32_t* dims, int Hq, int Hkv, int64_t q_stride_tok,
-                                int64_t q_stride_head, int64_t kv_stride_slot, const int32_t* cache_loc, int n_new,
-                                int64_t new_stride_tok, void* plan, size_t plan_bytes, void* stream) {
-    if (NE < 0 || P < 0 || total_kv < 0 || total_kv > 0x7fffffffLL || !plan || Hq <= 0 || Hkv <= 0 || Hq % Hkv ||
-        (NE > 0 && (!node_kv || !node_kv_offset || !node_kv_len || !node_q || !node_q_offset || !node_q_len))) {
-        set_error("bad node plan arguments (NE=%d P=%d total_kv=%lld)", NE, P, (long long)total_kv);
-        return DEFT_EINVAL;
-    }
-    const int64_t tiles = node_max_tiles(NE, total_kv);
-    const int64_t rows = tiles * node_rows_per_tile(P);
-    const PlanView pv = plan_view(plan, tiles * (Hq / Hkv), rows);
-    if (plan_bytes < pv.bytes) {
-        set_error("plan buffer too small: %zu < %zu", plan_bytes, pv.bytes);
-        return DEFT_EWORKSPACE;
+// Shared body of the three Node plan builders, behind their argument checks (`dims`, `win`: as in flatten_build_plan_impl).
+static int node_build_plan_impl(const NodeMd& md, const Tensors& t, const int32_t* cache_loc, int n_new, int64_t new_stride_tok,
+                                void* plan, size_t plan_bytes, void* stream, const int32_t* dims, const WindowArgs* win = nullptr) {
+    const PlanView pv = md.plan(plan, t.G());
+    int rc = plan_holds(plan_bytes, pv.bytes);
+    if (rc) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (win) {
+        // (writable arrays of the window entry point, as in flatten_build_plan_impl: this launch appends the step's overflow entries)
+        auto w = [](const int64_t* a) { return const_cast<int64_t*>(a); };
+        TreeMdOut o{w(md.node_q), w(md.node_kv), w(md.node_q_len), w(md.node_kv_len), w(md.node_q_offset), w(md.node_kv_offset),
+                    nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        hipLaunchKernelGGL(window_entries_kernel, dim3(1), dim3(256), 0, st, o, win->dims, win->nq, win->max_q_len, win->win_tiles, md.NE,
+                           md.P, (int)md.total_kv);
+        rc = check_launch("window entries launch");
+        if (rc) return rc;
     }
     Stage1Params p{};
-    p.node_kv = node_kv;
-    p.node_kv_offset = node_kv_offset;
-    p.node_kv_len = node_kv_len;
-    p.node_q = node_q;
-    p.node_q_offset = node_q_offset;
-    p.node_q_len = node_q_len;
-    p.rows = rows;
-    p.G = Hq / Hkv;
-    p.Hkv = Hkv;
-    p.q_st = q_stride_tok;
-    p.q_sh = q_stride_head;
-    p.kv_ss = kv_stride_slot;
+    t.fill(p);
+    md.fill(p);
     AppendArgs ap;  // only the slots of this step's new rows and their stride matter to the plan
     if (cache_loc) {
         if (n_new < 0 || new_stride_tok < 0) {
             set_error("bad node plan append arguments (n_new=%d)", n_new);
             return DEFT_EINVAL;
         }
-        ap.cache_loc = cache_loc;
-        ap.n_new = n_new;
-        ap.new_st = new_stride_tok;
+        ap = plan_append(cache_loc, n_new, new_stride_tok);
     }
-    return launch_node_plan(p, NE, rows, pv, ap, static_cast<hipStream_t>(stream), 0, dims);
+    return launch_node_plan(p, md.NE, md.rows(), pv, ap, st, 0, dims, win ? win->win_tiles : 0, win ? win->win_tab : nullptr);
+}
+static int check_node_plan_args(const NodeMd& md, const Tensors& t, const void* plan) {
+    if (md.ok() && plan && t.heads_ok()) return DEFT_OK;
+    set_error("bad node plan arguments (NE=%d P=%d total_kv=%lld)", md.NE, md.P, (long long)md.total_kv);
+    return DEFT_EINVAL;
 }
 
 int deft_node_build_plan(const int64_t* node_kv, const int64_t* node_kv_offset, const int64_t* node_kv_len,
@@ -1393,9 +1186,10 @@ int deft_node_build_plan(const int64_t* node_kv, const int64_t* node_kv_offset, 
                          int64_t total_kv, int Hq, int Hkv, int64_t q_stride_tok, int64_t q_stride_head,
                          int64_t kv_stride_slot, const int32_t* cache_loc, int n_new, int64_t new_stride_tok, void* plan,
                          size_t plan_bytes, void* stream) {
-    return node_build_plan_impl(node_kv, node_kv_offset, node_kv_len, node_q, node_q_offset, node_q_len, NE, P, total_kv, nullptr, Hq,
-                                Hkv, q_stride_tok, q_stride_head, kv_stride_slot, cache_loc, n_new, new_stride_tok, plan, plan_bytes,
-                                stream);
+    const NodeMd md{node_kv, node_kv_offset, node_kv_len, node_q, node_q_offset, node_q_len, NE, P, total_kv, 0};
+    const Tensors t = plan_geometry(Hq, Hkv, q_stride_tok, q_stride_head, kv_stride_slot);
+    if (int rc = check_node_plan_args(md, t, plan)) return rc;
+    return node_build_plan_impl(md, t, cache_loc, n_new, new_stride_tok, plan, plan_bytes, stream, nullptr);
 }
 
 // Node-mode counterpart of deft_flatten_build_plan_dims: NE, P, total_kv are the CAPACITIES of the device-built arrays, this
@@ -1409,165 +1203,67 @@ int deft_node_build_plan_dims(const int64_t* node_kv, const int64_t* node_kv_off
         set_error("deft_node_build_plan_dims: null dims");
         return DEFT_EINVAL;
     }
-    return node_build_plan_impl(node_kv, node_kv_offset, node_kv_len, node_q, node_q_offset, node_q_len, NE, P, total_kv, dims, Hq,
-                                Hkv, q_stride_tok, q_stride_head, kv_stride_slot, cache_loc, n_new, new_stride_tok, plan, plan_bytes,
-                                stream);
+    const NodeMd md{node_kv, node_kv_offset, node_kv_len, node_q, node_q_offset, node_q_len, NE, P, total_kv, 0};
+    const Tensors t = plan_geometry(Hq, Hkv, q_stride_tok, q_stride_head, kv_stride_slot);
+    if (int rc = check_node_plan_args(md, t, plan)) return rc;
+    return node_build_plan_impl(md, t, cache_loc, n_new, new_stride_tok, plan, plan_bytes, stream, dims);
 }
-
 
 }  // extern "C"
 
 template <class T>
-static int node_decode_impl(const void* q, int64_t q_stride_tok, int64_t q_stride_head, const void* k_base,
-                            const void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head, void* out,
-                            int64_t o_stride_tok, int64_t o_stride_head, const int64_t* node_kv,
-                            const int64_t* node_kv_offset, const int64_t* node_kv_len, const int64_t* node_q,
-                            const int64_t* node_q_offset, const int64_t* node_q_len, int NE, int P, int64_t total_kv, int nq,
-                            int Hq, int Hkv, int D, float scale, const void* plan, void* workspace, size_t workspace_bytes,
-                            void* stream, const AppendArgs& ap, int rows_per_tile = 0 /* 0: from P; 1: the sequential comparator */) {
-    int rc = check_common(q, q_stride_tok, q_stride_head, k_base, v_base, kv_stride_slot, kv_stride_head, out,
-                          o_stride_tok, o_stride_head, nq, Hq, Hkv, D);
+static int node_decode_impl(const Tensors& t, const NodeMd& md, const AppendArgs& ap, const Scratch& sc) {
+    int rc = t.check();
     if (rc) return rc;
-    if (NE < 0 || P < 0 || total_kv < 0 || total_kv > 0x7fffffffLL ||
-        (NE > 0 && (!node_kv || !node_kv_offset || !node_kv_len || !node_q || !node_q_offset || !node_q_len))) {
-        set_error("bad Node metadata (NE=%d P=%d total_kv=%lld)", NE, P, (long long)total_kv);
-        return DEFT_EINVAL;
-    }
-    if (!workspace) {
-        set_error("null workspace");
-        return DEFT_EINVAL;
-    }
-    rc = check_append(ap, Hkv, D);
+    rc = md.check();
     if (rc) return rc;
-    const int G = Hq / Hkv;
-    const int64_t tiles = node_max_tiles(NE, total_kv);
-    const int64_t rows = tiles * (rows_per_tile > 0 ? rows_per_tile : node_rows_per_tile(P));  // every entry has at most that many queries
-    const Workspace ws = carve(workspace, Hq, D, rows, tiles, plan_view(nullptr, tiles * G, rows).bytes);
-    if (workspace_bytes < ws.bytes) {
-        set_error("workspace too small: %zu < %zu", workspace_bytes, ws.bytes);
-        return DEFT_EWORKSPACE;
-    }
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    rc = sc.check();
+    if (rc) return rc;
+    rc = ap.check(t.Hkv, t.D);
+    if (rc) return rc;
+    const int G = t.G();
+    const int64_t tiles = md.tiles(), rows = md.rows();
+    const Workspace ws = carve(sc.workspace, t.Hq, t.D, rows, tiles, md.plan(nullptr, G).bytes);
+    rc = sc.holds(ws);
+    if (rc) return rc;
+    hipStream_t st = sc.st();
     Stage1Params p{};
-    p.q = static_cast<const e16*>(q);
-    p.q_st = q_stride_tok;
-    p.q_sh = q_stride_head;
-    p.k = static_cast<const e16*>(k_base);
-    p.v = static_cast<const e16*>(v_base);
-    p.kv_ss = kv_stride_slot;
-    p.kv_sh = kv_stride_head;
-    p.node_kv = node_kv;
-    p.node_kv_offset = node_kv_offset;
-    p.node_kv_len = node_kv_len;
-    p.node_q = node_q;
-    p.node_q_offset = node_q_offset;
-    p.node_q_len = node_q_len;
+    t.fill(p);
+    md.fill(p);
     p.partial_o = ws.partial_o;
     p.partial_lse = ws.partial_lse;
     p.row_q = ws.row_q;
-    p.rows = rows;
-    p.Hkv = Hkv;
-    p.G = G;
-    p.scale_log2e = scale * LOG2E;
-    const bool hd2 = hd2_geometry(D, Hkv, kv_stride_head) && !ap.cos_sin && rows_per_tile != 1;
-    if (D == 128 || hd2) {
+    const bool seq = md.rows_per_tile == 1;
+    const bool hd2 = hd2_geometry(t.D, t.Hkv, t.kv_sh) && !ap.cos_sin && !seq;
+    if (t.D == 128 || hd2) {
         PlanView pv;
-        if (plan) {
-            pv = plan_view(const_cast<void*>(plan), tiles * G, rows);
+        if (sc.plan) {
+            pv = md.plan(const_cast<void*>(sc.plan), G);
         } else {
-            pv = plan_view(ws.plan, tiles * G, rows);
-            rc = launch_node_plan(p, NE, rows, pv, ap, st);
+            pv = md.plan(ws.plan, G);
+            rc = launch_node_plan(p, md.NE, rows, pv, ap, st);
             if (rc) return rc;
         }
-        rc = launch_stage1_np<T>(p, tiles * G, pv, ap, st, nq, /*reread=*/rows_per_tile == 1, hd2);
+        rc = launch_stage1_np<T>(p, tiles * G, pv, ap, st, t.nq, /*reread=*/seq, hd2);
         if (rc) return rc;
-        return launch_merge<T>(D, ws, &pv, pv.row_q, rows, out, o_stride_tok, o_stride_head, nq, Hq, G * (hd2 ? 2 : 1), st);
+        return launch_merge<T>(t.D, ws, &pv, pv.row_q, rows, t.out, t.o_st, t.o_sh, t.nq, t.Hq, G * (hd2 ? 2 : 1), st);
     }
     // tile-per-workgroup form (head_dim 64)
-    if (ap.k_new) {  // separate append launch first
-        rc = kv_append_impl(const_cast<void*>(k_base), const_cast<void*>(v_base), kv_stride_slot, kv_stride_head,
-                                ap.cache_loc, ap.k_new, ap.v_new, ap.new_st, ap.n_new, Hkv, D, stream);
-        if (rc) return rc;
-    }
-    const size_t prep_lds = sizeof(int) * 2 * (size_t)(NE + 1);
+    rc = append_first(t, ap, sc.stream);
+    if (rc) return rc;
+    const size_t prep_lds = sizeof(int) * 2 * (size_t)(md.NE + 1);
     if (prep_lds > 64 * 1024) {
-        set_error("node mode: %d entries exceed the prep kernel's LDS scan", NE);
+        set_error("node mode: %d entries exceed the prep kernel's LDS scan", md.NE);
         return DEFT_EUNSUPPORTED;
     }
-    hipLaunchKernelGGL(node_prep_kernel, dim3(1), dim3(256), prep_lds, st, node_kv_offset, node_kv_len, node_q_offset,
-                       node_q_len, NE, tiles, rows, ws.desc, ws.row_q);
+    hipLaunchKernelGGL(node_prep_kernel, dim3(1), dim3(256), prep_lds, st, md.node_kv_offset, md.node_kv_len, md.node_q_offset,
+                       md.node_q_len, md.NE, tiles, rows, ws.desc, ws.row_q);
     rc = check_launch("node prep launch");
     if (rc) return rc;
     p.desc = ws.desc;
-    rc = launch_stage1_d64<T, 1>(D, p, tiles, st);
+    rc = launch_stage1_d64<T, 1>(t.D, p, tiles, st);
     if (rc) return rc;
-    return launch_merge<T>(D, ws, nullptr, ws.row_q, rows, out, o_stride_tok, o_stride_head, nq, Hq, 1, st);
-}
-
-
-template <class T>
-static int node_decode_t(const void* q, int64_t q_stride_tok, int64_t q_stride_head, const void* k_base,
-                         const void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head, void* out,
-                         int64_t o_stride_tok, int64_t o_stride_head, const int64_t* node_kv,
-                         const int64_t* node_kv_offset, const int64_t* node_kv_len, const int64_t* node_q,
-                         const int64_t* node_q_offset, const int64_t* node_q_len, int NE, int P, int64_t total_kv, int nq,
-                         int Hq, int Hkv, int D, float scale, const void* plan, void* workspace, size_t workspace_bytes,
-                         void* stream) {
-    return node_decode_impl<T>(q, q_stride_tok, q_stride_head, k_base, v_base, kv_stride_slot, kv_stride_head, out,
-                            o_stride_tok, o_stride_head, node_kv, node_kv_offset, node_kv_len, node_q, node_q_offset,
-                            node_q_len, NE, P, total_kv, nq, Hq, Hkv, D, scale, plan, workspace, workspace_bytes, stream,
-                            AppendArgs());
-}
-
-template <class T>
-static int node_decode_append_t(const void* q, int64_t q_stride_tok, int64_t q_stride_head, void* k_base, void* v_base,
-                                int64_t kv_stride_slot, int64_t kv_stride_head, void* out, int64_t o_stride_tok,
-                                int64_t o_stride_head, const int64_t* node_kv, const int64_t* node_kv_offset,
-                                const int64_t* node_kv_len, const int64_t* node_q, const int64_t* node_q_offset,
-                                const int64_t* node_q_len, int NE, int P, int64_t total_kv, int nq, int Hq, int Hkv, int D,
-                                float scale, const int32_t* cache_loc, const void* k_new, const void* v_new,
-                                int64_t new_stride_tok, int n_new, const void* plan, void* workspace,
-                                size_t workspace_bytes, void* stream) {
-    AppendArgs ap;
-    ap.k_new = static_cast<const e16*>(k_new);
-    ap.v_new = static_cast<const e16*>(v_new);
-    ap.cache_loc = cache_loc;
-    ap.new_st = new_stride_tok;
-    ap.n_new = n_new;
-    if (!k_new || !v_new || !cache_loc) {
-        set_error("fused append needs k_new, v_new and cache_loc");
-        return DEFT_EINVAL;
-    }
-    return node_decode_impl<T>(q, q_stride_tok, q_stride_head, k_base, v_base, kv_stride_slot, kv_stride_head, out,
-                            o_stride_tok, o_stride_head, node_kv, node_kv_offset, node_kv_len, node_q, node_q_offset,
-                            node_q_len, NE, P, total_kv, nq, Hq, Hkv, D, scale, plan, workspace, workspace_bytes, stream, ap);
-}
-
-template <class T>
-static int node_decode_rope_append_t(const void* q, int64_t q_stride_tok, int64_t q_stride_head, void* k_base, void* v_base,
-                                     int64_t kv_stride_slot, int64_t kv_stride_head, void* out, int64_t o_stride_tok,
-                                     int64_t o_stride_head, const int64_t* node_kv, const int64_t* node_kv_offset,
-                                     const int64_t* node_kv_len, const int64_t* node_q, const int64_t* node_q_offset,
-                                     const int64_t* node_q_len, int NE, int P, int64_t total_kv, int nq, int Hq, int Hkv, int D,
-                                     float scale, const int32_t* cache_loc, const void* k_new, const void* v_new,
-                                     int64_t new_stride_tok, int n_new, const float* cos_sin_rows, int rotary_dim,
-                                     int is_neox_style, const void* plan, void* workspace, size_t workspace_bytes,
-                                     void* stream) {
-    AppendArgs ap;
-    ap.k_new = static_cast<const e16*>(k_new);
-    ap.v_new = static_cast<const e16*>(v_new);
-    ap.cache_loc = cache_loc;
-    ap.new_st = new_stride_tok;
-    ap.n_new = n_new;
-    if (!k_new || !v_new || !cache_loc) {
-        set_error("fused append needs k_new, v_new and cache_loc");
-        return DEFT_EINVAL;
-    }
-    const int rc = fill_rope(ap, cos_sin_rows, rotary_dim, is_neox_style, q_stride_tok, q_stride_head, Hq, D);
-    if (rc) return rc;
-    return node_decode_impl<T>(q, q_stride_tok, q_stride_head, k_base, v_base, kv_stride_slot, kv_stride_head, out,
-                            o_stride_tok, o_stride_head, node_kv, node_kv_offset, node_kv_len, node_q, node_q_offset,
-                            node_q_len, NE, P, total_kv, nq, Hq, Hkv, D, scale, plan, workspace, workspace_bytes, stream, ap);
+    return launch_merge<T>(t.D, ws, nullptr, ws.row_q, rows, t.out, t.o_st, t.o_sh, t.nq, t.Hq, 1, st);
 }
 
 static int kv_append_impl(void* k_base, void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head,
@@ -1663,6 +1359,10 @@ struct SeqPlan {  // [node plan | node_kv | node_kv_offset | node_kv_len | node_
     size_t node_plan_bytes;
     int64_t *node_kv, *node_kv_offset, *node_kv_len, *node_q, *node_q_offset, *node_q_len;
     size_t bytes;
+    // request i is entry i with the one query row i: a partial row per tile
+    NodeMd node_md(int nq, int64_t total) const {
+        return NodeMd{node_kv, node_kv_offset, node_kv_len, node_q, node_q_offset, node_q_len, nq, nq, total, 1};
+    }
 };
 static SeqPlan seq_plan_view(void* base, int nq, int64_t total, int Hq, int Hkv) {
     SeqPlan v;
@@ -1729,80 +1429,27 @@ int deft_seq_build_plan(const int32_t* req_to_token, int64_t req_stride, const i
                        sp.node_q_offset, sp.node_q_len, static_cast<int32_t*>(sp.node_plan));
     int rc = check_launch("seq_to_node launch");
     if (rc) return rc;
-    const int64_t tiles = node_max_tiles(nq, total_tokens);
-    const PlanView pv = plan_view(sp.node_plan, tiles * (Hq / Hkv), tiles);
+    const NodeMd md = sp.node_md(nq, total_tokens);
+    const Tensors t = plan_geometry(Hq, Hkv, q_stride_tok, q_stride_head, kv_stride_slot);
     Stage1Params p{};
-    p.node_kv = sp.node_kv;
-    p.node_kv_offset = sp.node_kv_offset;
-    p.node_kv_len = sp.node_kv_len;
-    p.node_q = sp.node_q;
-    p.node_q_offset = sp.node_q_offset;
-    p.node_q_len = sp.node_q_len;
-    p.rows = tiles;
-    p.G = Hq / Hkv;
-    p.Hkv = Hkv;
-    p.q_st = q_stride_tok;
-    p.q_sh = q_stride_head;
-    p.kv_ss = kv_stride_slot;
-    AppendArgs ap;
-    if (cache_loc) {
-        ap.cache_loc = cache_loc;
-        ap.n_new = n_new;
-        ap.new_st = new_stride_tok;
-    }
-    return launch_node_plan(p, nq, tiles, pv, ap, st, 1);
+    t.fill(p);
+    md.fill(p);
+    const AppendArgs ap = cache_loc ? plan_append(cache_loc, n_new, new_stride_tok) : AppendArgs();
+    return launch_node_plan(p, nq, md.rows(), md.plan(sp.node_plan, t.G()), ap, st, 1);
 }
 
 }  // extern "C"
 
 template <class T>
-static int seq_decode_impl(const void* q, int64_t q_stride_tok, int64_t q_stride_head, const void* k_base,
-                           const void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head, void* out,
-                           int64_t o_stride_tok, int64_t o_stride_head, const void* plan, int nq, int64_t total_tokens,
-                           int Hq, int Hkv, int D, float scale, void* workspace, size_t workspace_bytes, void* stream,
-                           const AppendArgs& ap) {
-    if (!plan || nq < 0 || total_tokens < 0 || Hq <= 0 || Hkv <= 0 || Hq % Hkv) {
-        set_error("bad sequential decode arguments (nq=%d total_tokens=%lld)", nq, (long long)total_tokens);
+static int seq_decode_impl(const Tensors& t, int64_t total_tokens, const AppendArgs& ap, const Scratch& sc) {
+    if (!sc.plan || t.nq < 0 || total_tokens < 0 || !t.heads_ok()) {
+        set_error("bad sequential decode arguments (nq=%d total_tokens=%lld)", t.nq, (long long)total_tokens);
         return DEFT_EINVAL;
     }
-    const SeqPlan sp = seq_plan_view(const_cast<void*>(plan), nq, total_tokens, Hq, Hkv);
-    return node_decode_impl<T>(q, q_stride_tok, q_stride_head, k_base, v_base, kv_stride_slot, kv_stride_head, out,
-                            o_stride_tok, o_stride_head, sp.node_kv, sp.node_kv_offset, sp.node_kv_len, sp.node_q,
-                            sp.node_q_offset, sp.node_q_len, nq, nq, total_tokens, nq, Hq, Hkv, D, scale,
-                            D == 128 ? sp.node_plan : nullptr, workspace, workspace_bytes, stream, ap, 1);
+    const SeqPlan sp = seq_plan_view(const_cast<void*>(sc.plan), t.nq, total_tokens, t.Hq, t.Hkv);
+    return node_decode_impl<T>(t, sp.node_md(t.nq, total_tokens), ap,
+                               Scratch{t.D == 128 ? sp.node_plan : nullptr, sc.workspace, sc.workspace_bytes, sc.stream});
 }
-
-template <class T>
-static int seq_decode_t(const void* q, int64_t q_stride_tok, int64_t q_stride_head, const void* k_base, const void* v_base,
-                        int64_t kv_stride_slot, int64_t kv_stride_head, void* out, int64_t o_stride_tok,
-                        int64_t o_stride_head, const void* plan, int nq, int64_t total_tokens, int Hq, int Hkv, int D,
-                        float scale, void* workspace, size_t workspace_bytes, void* stream) {
-    return seq_decode_impl<T>(q, q_stride_tok, q_stride_head, k_base, v_base, kv_stride_slot, kv_stride_head, out,
-                           o_stride_tok, o_stride_head, plan, nq, total_tokens, Hq, Hkv, D, scale, workspace,
-                           workspace_bytes, stream, AppendArgs());
-}
-
-template <class T>
-static int seq_decode_append_t(const void* q, int64_t q_stride_tok, int64_t q_stride_head, void* k_base, void* v_base,
-                               int64_t kv_stride_slot, int64_t kv_stride_head, void* out, int64_t o_stride_tok,
-                               int64_t o_stride_head, const void* plan, int nq, int64_t total_tokens, int Hq, int Hkv,
-                               int D, float scale, const int32_t* cache_loc, const void* k_new, const void* v_new,
-                               int64_t new_stride_tok, int n_new, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!k_new || !v_new || !cache_loc) {
-        set_error("fused append needs k_new, v_new and cache_loc");
-        return DEFT_EINVAL;
-    }
-    AppendArgs ap;
-    ap.k_new = static_cast<const e16*>(k_new);
-    ap.v_new = static_cast<const e16*>(v_new);
-    ap.cache_loc = cache_loc;
-    ap.new_st = new_stride_tok;
-    ap.n_new = n_new;
-    return seq_decode_impl<T>(q, q_stride_tok, q_stride_head, k_base, v_base, kv_stride_slot, kv_stride_head, out,
-                           o_stride_tok, o_stride_head, plan, nq, total_tokens, Hq, Hkv, D, scale, workspace,
-                           workspace_bytes, stream, ap);
-}
-
 
 
 // ---------------------------------------------------------------------------
@@ -1963,84 +1610,99 @@ static int prefill_t(const void* q, int64_t q_stride_tok, int64_t q_stride_head,
 // The data entry points of include/deft_amd.h: every one exists for IEEE binary16 (_f16) and for bfloat16 (_bf16),
 // the same parameter list, the same body instantiated for the element type.
 // ---------------------------------------------------------------------------
-#define DEFT_TWINS(name, params, args)                                        \
-    extern "C" int deft_##name##_f16 params { return name##_t<F16> args; }    \
-    extern "C" int deft_##name##_bf16 params { return name##_t<BF16> args; }
+// A body is written once, with T the element traits.  The parameter names are the same in every signature, so each struct of
+// call.h is packed by one expression.
+#define DEFT_TWINS(name, params, ...)                                              \
+    extern "C" int deft_##name##_f16 params { using T = F16; __VA_ARGS__ }         \
+    extern "C" int deft_##name##_bf16 params { using T = BF16; __VA_ARGS__ }
+#define TENSORS \
+    Tensors{q, q_stride_tok, q_stride_head, k_base, v_base, kv_stride_slot, kv_stride_head, out, o_stride_tok, o_stride_head, nq, Hq, Hkv, D, scale}
+#define FLATTEN_MD FlattenMd{block_q, block_q_cnts, block_q_offset, block_bitmasks, block_kv, block_lens, NB, P}
+#define NODE_MD NodeMd{node_kv, node_kv_offset, node_kv_len, node_q, node_q_offset, node_q_len, NE, P, total_kv, 0}
+#define SCRATCH Scratch{plan, workspace, workspace_bytes, stream}
+#define APPEND cache_loc, k_new, v_new, new_stride_tok, n_new
+#define ROPE cos_sin_rows, rotary_dim, is_neox_style
 DEFT_TWINS(flatten_decode, (const void* q, int64_t q_stride_tok, int64_t q_stride_head, const void* k_base, const void*
             v_base, int64_t kv_stride_slot, int64_t kv_stride_head, void* out, int64_t o_stride_tok, int64_t o_stride_head,
             const int64_t* block_q, const int64_t* block_q_cnts, const int64_t* block_q_offset, const int64_t* block_bitmasks,
             const int64_t* block_kv, const int64_t* block_lens, int NB, int P, int nq, int Hq, int Hkv, int D, float scale,
-            const void* plan, void* workspace, size_t workspace_bytes, void* stream), (q, q_stride_tok, q_stride_head, k_base,
-            v_base, kv_stride_slot, kv_stride_head, out, o_stride_tok, o_stride_head, block_q, block_q_cnts, block_q_offset,
-            block_bitmasks, block_kv, block_lens, NB, P, nq, Hq, Hkv, D, scale, plan, workspace, workspace_bytes, stream))
+            const void* plan, void* workspace, size_t workspace_bytes, void* stream),
+           { return flatten_decode_impl<T>(TENSORS, FLATTEN_MD, AppendArgs(), SCRATCH); })
 DEFT_TWINS(flatten_decode_append, (const void* q, int64_t q_stride_tok, int64_t q_stride_head, void* k_base, void* v_base,
             int64_t kv_stride_slot, int64_t kv_stride_head, void* out, int64_t o_stride_tok, int64_t o_stride_head, const
             int64_t* block_q, const int64_t* block_q_cnts, const int64_t* block_q_offset, const int64_t* block_bitmasks, const
             int64_t* block_kv, const int64_t* block_lens, int NB, int P, int nq, int Hq, int Hkv, int D, float scale, const
             int32_t* cache_loc, const void* k_new, const void* v_new, int64_t new_stride_tok, int n_new, const void* plan,
-            void* workspace, size_t workspace_bytes, void* stream), (q, q_stride_tok, q_stride_head, k_base, v_base,
-            kv_stride_slot, kv_stride_head, out, o_stride_tok, o_stride_head, block_q, block_q_cnts, block_q_offset,
-            block_bitmasks, block_kv, block_lens, NB, P, nq, Hq, Hkv, D, scale, cache_loc, k_new, v_new, new_stride_tok,
-            n_new, plan, workspace, workspace_bytes, stream))
+            void* workspace, size_t workspace_bytes, void* stream), {
+    AppendArgs ap;
+    if (int rc = make_append(ap, APPEND)) return rc;
+    return flatten_decode_impl<T>(TENSORS, FLATTEN_MD, ap, SCRATCH);
+})
 DEFT_TWINS(node_decode, (const void* q, int64_t q_stride_tok, int64_t q_stride_head, const void* k_base, const void* v_base,
             int64_t kv_stride_slot, int64_t kv_stride_head, void* out, int64_t o_stride_tok, int64_t o_stride_head, const
             int64_t* node_kv, const int64_t* node_kv_offset, const int64_t* node_kv_len, const int64_t* node_q, const int64_t*
             node_q_offset, const int64_t* node_q_len, int NE, int P, int64_t total_kv, int nq, int Hq, int Hkv, int D, float
-            scale, const void* plan, void* workspace, size_t workspace_bytes, void* stream), (q, q_stride_tok, q_stride_head,
-            k_base, v_base, kv_stride_slot, kv_stride_head, out, o_stride_tok, o_stride_head, node_kv, node_kv_offset,
-            node_kv_len, node_q, node_q_offset, node_q_len, NE, P, total_kv, nq, Hq, Hkv, D, scale, plan, workspace,
-            workspace_bytes, stream))
+            scale, const void* plan, void* workspace, size_t workspace_bytes, void* stream),
+           { return node_decode_impl<T>(TENSORS, NODE_MD, AppendArgs(), SCRATCH); })
 DEFT_TWINS(node_decode_append, (const void* q, int64_t q_stride_tok, int64_t q_stride_head, void* k_base, void* v_base,
             int64_t kv_stride_slot, int64_t kv_stride_head, void* out, int64_t o_stride_tok, int64_t o_stride_head, const
             int64_t* node_kv, const int64_t* node_kv_offset, const int64_t* node_kv_len, const int64_t* node_q, const int64_t*
             node_q_offset, const int64_t* node_q_len, int NE, int P, int64_t total_kv, int nq, int Hq, int Hkv, int D, float
             scale, const int32_t* cache_loc, const void* k_new, const void* v_new, int64_t new_stride_tok, int n_new, const
-            void* plan, void* workspace, size_t workspace_bytes, void* stream), (q, q_stride_tok, q_stride_head, k_base,
-            v_base, kv_stride_slot, kv_stride_head, out, o_stride_tok, o_stride_head, node_kv, node_kv_offset, node_kv_len,
-            node_q, node_q_offset, node_q_len, NE, P, total_kv, nq, Hq, Hkv, D, scale, cache_loc, k_new, v_new,
-            new_stride_tok, n_new, plan, workspace, workspace_bytes, stream))
+            void* plan, void* workspace, size_t workspace_bytes, void* stream), {
+    AppendArgs ap;
+    if (int rc = make_append(ap, APPEND)) return rc;
+    return node_decode_impl<T>(TENSORS, NODE_MD, ap, SCRATCH);
+})
 DEFT_TWINS(flatten_decode_rope_append, (const void* q, int64_t q_stride_tok, int64_t q_stride_head, void* k_base, void*
             v_base, int64_t kv_stride_slot, int64_t kv_stride_head, void* out, int64_t o_stride_tok, int64_t o_stride_head,
             const int64_t* block_q, const int64_t* block_q_cnts, const int64_t* block_q_offset, const int64_t* block_bitmasks,
             const int64_t* block_kv, const int64_t* block_lens, int NB, int P, int nq, int Hq, int Hkv, int D, float scale,
             const int32_t* cache_loc, const void* k_new, const void* v_new, int64_t new_stride_tok, int n_new, const float*
             cos_sin_rows, int rotary_dim, int is_neox_style, const void* plan, void* workspace, size_t workspace_bytes, void*
-            stream), (q, q_stride_tok, q_stride_head, k_base, v_base, kv_stride_slot, kv_stride_head, out, o_stride_tok,
-            o_stride_head, block_q, block_q_cnts, block_q_offset, block_bitmasks, block_kv, block_lens, NB, P, nq, Hq, Hkv, D,
-            scale, cache_loc, k_new, v_new, new_stride_tok, n_new, cos_sin_rows, rotary_dim, is_neox_style, plan, workspace,
-            workspace_bytes, stream))
+            stream), {
+    const Tensors t = TENSORS;
+    AppendArgs ap;
+    if (int rc = make_append(ap, APPEND, ROPE, t)) return rc;
+    return flatten_decode_impl<T>(t, FLATTEN_MD, ap, SCRATCH);
+})
 DEFT_TWINS(node_decode_rope_append, (const void* q, int64_t q_stride_tok, int64_t q_stride_head, void* k_base, void* v_base,
             int64_t kv_stride_slot, int64_t kv_stride_head, void* out, int64_t o_stride_tok, int64_t o_stride_head, const
             int64_t* node_kv, const int64_t* node_kv_offset, const int64_t* node_kv_len, const int64_t* node_q, const int64_t*
             node_q_offset, const int64_t* node_q_len, int NE, int P, int64_t total_kv, int nq, int Hq, int Hkv, int D, float
             scale, const int32_t* cache_loc, const void* k_new, const void* v_new, int64_t new_stride_tok, int n_new, const
             float* cos_sin_rows, int rotary_dim, int is_neox_style, const void* plan, void* workspace, size_t workspace_bytes,
-            void* stream), (q, q_stride_tok, q_stride_head, k_base, v_base, kv_stride_slot, kv_stride_head, out, o_stride_tok,
-            o_stride_head, node_kv, node_kv_offset, node_kv_len, node_q, node_q_offset, node_q_len, NE, P, total_kv, nq, Hq,
-            Hkv, D, scale, cache_loc, k_new, v_new, new_stride_tok, n_new, cos_sin_rows, rotary_dim, is_neox_style, plan,
-            workspace, workspace_bytes, stream))
+            void* stream), {
+    const Tensors t = TENSORS;
+    AppendArgs ap;
+    if (int rc = make_append(ap, APPEND, ROPE, t)) return rc;
+    return node_decode_impl<T>(t, NODE_MD, ap, SCRATCH);
+})
 DEFT_TWINS(prefill, (const void* q, int64_t q_stride_tok, int64_t q_stride_head, const void* k, int64_t k_stride_tok, int64_t
             k_stride_head, const void* v, int64_t v_stride_tok, int64_t v_stride_head, void* out, int64_t o_stride_tok,
             int64_t o_stride_head, const int32_t* b_start_loc, const int32_t* b_seq_len, int batch, int max_input_len, int Hq,
-            int Hkv, int D, float scale, void* stream), (q, q_stride_tok, q_stride_head, k, k_stride_tok, k_stride_head, v,
-            v_stride_tok, v_stride_head, out, o_stride_tok, o_stride_head, b_start_loc, b_seq_len, batch, max_input_len, Hq,
-            Hkv, D, scale, stream))
+            int Hkv, int D, float scale, void* stream),
+           { return prefill_t<T>(q, q_stride_tok, q_stride_head, k, k_stride_tok, k_stride_head, v, v_stride_tok,
+                                 v_stride_head, out, o_stride_tok, o_stride_head, b_start_loc, b_seq_len, batch, max_input_len, Hq,
+                                 Hkv, D, scale, stream); })
 DEFT_TWINS(rope_qk, (void* q, int64_t q_stride_tok, int64_t q_stride_head, int Hq, void* k, int64_t k_stride_tok, int64_t
             k_stride_head, int Hk, const int64_t* positions, const float* cos_sin_cache, int64_t cache_stride, int n, int D,
-            int rotary_dim, int is_neox_style, void* stream), (q, q_stride_tok, q_stride_head, Hq, k, k_stride_tok,
-            k_stride_head, Hk, positions, cos_sin_cache, cache_stride, n, D, rotary_dim, is_neox_style, stream))
+            int rotary_dim, int is_neox_style, void* stream),
+           { return rope_qk_t<T>(q, q_stride_tok, q_stride_head, Hq, k, k_stride_tok, k_stride_head, Hk,
+                                 positions, cos_sin_cache, cache_stride, n, D, rotary_dim, is_neox_style, stream); })
 DEFT_TWINS(seq_decode, (const void* q, int64_t q_stride_tok, int64_t q_stride_head, const void* k_base, const void* v_base,
             int64_t kv_stride_slot, int64_t kv_stride_head, void* out, int64_t o_stride_tok, int64_t o_stride_head, const
             void* plan, int nq, int64_t total_tokens, int Hq, int Hkv, int D, float scale, void* workspace, size_t
-            workspace_bytes, void* stream), (q, q_stride_tok, q_stride_head, k_base, v_base, kv_stride_slot, kv_stride_head,
-            out, o_stride_tok, o_stride_head, plan, nq, total_tokens, Hq, Hkv, D, scale, workspace, workspace_bytes, stream))
+            workspace_bytes, void* stream),
+           { return seq_decode_impl<T>(TENSORS, total_tokens, AppendArgs(), SCRATCH); })
 DEFT_TWINS(seq_decode_append, (const void* q, int64_t q_stride_tok, int64_t q_stride_head, void* k_base, void* v_base, int64_t
             kv_stride_slot, int64_t kv_stride_head, void* out, int64_t o_stride_tok, int64_t o_stride_head, const void* plan,
             int nq, int64_t total_tokens, int Hq, int Hkv, int D, float scale, const int32_t* cache_loc, const void* k_new,
-            const void* v_new, int64_t new_stride_tok, int n_new, void* workspace, size_t workspace_bytes, void* stream), (q,
-            q_stride_tok, q_stride_head, k_base, v_base, kv_stride_slot, kv_stride_head, out, o_stride_tok, o_stride_head,
-            plan, nq, total_tokens, Hq, Hkv, D, scale, cache_loc, k_new, v_new, new_stride_tok, n_new, workspace,
-            workspace_bytes, stream))
+            const void* v_new, int64_t new_stride_tok, int n_new, void* workspace, size_t workspace_bytes, void* stream), {
+    AppendArgs ap;
+    if (int rc = make_append(ap, APPEND)) return rc;
+    return seq_decode_impl<T>(TENSORS, total_tokens, ap, SCRATCH);
+})
 extern "C" int deft_kv_append_f16(void* k_base, void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head, const int32_t* cache_loc,
                                   const void* k_new, const void* v_new, int64_t new_stride_tok, int n, int Hkv, int D, void* stream) {
     return kv_append_impl(k_base, v_base, kv_stride_slot, kv_stride_head, cache_loc, k_new, v_new, new_stride_tok, n, Hkv, D, stream);
@@ -2053,9 +1715,21 @@ DEFT_TWINS(flatten_stage1, (const void* q, int64_t q_stride_tok, int64_t q_strid
             v_base, int64_t kv_stride_slot, int64_t kv_stride_head, const int64_t* block_q, const int64_t* block_q_cnts, const
             int64_t* block_q_offset, const int64_t* block_bitmasks, const int64_t* block_kv, const int64_t* block_lens, int
             NB, int P, int nq, int Hq, int Hkv, int D, float scale, const void* plan, void* workspace, size_t workspace_bytes,
-            void* stream), (q, q_stride_tok, q_stride_head, k_base, v_base, kv_stride_slot, kv_stride_head, block_q,
-            block_q_cnts, block_q_offset, block_bitmasks, block_kv, block_lens, NB, P, nq, Hq, Hkv, D, scale, plan, workspace,
-            workspace_bytes, stream))
+            void* stream), {
+    const Scratch sc = SCRATCH;
+    if (int rc = sc.check()) return rc;
+    Workspace ws;
+    const int32_t* row_q = nullptr;
+    PlanView pv;
+    const Tensors t{q, q_stride_tok, q_stride_head, k_base, v_base, kv_stride_slot, kv_stride_head, nullptr, 0, 0, nq, Hq, Hkv, D, scale};
+    return flatten_stage1_impl<T>(t, FLATTEN_MD, AppendArgs(), sc, &ws, &row_q, &pv);
+})
+#undef ROPE
+#undef APPEND
+#undef SCRATCH
+#undef NODE_MD
+#undef FLATTEN_MD
+#undef TENSORS
 #undef DEFT_TWINS
 
 
@@ -2065,6 +1739,13 @@ DEFT_TWINS(flatten_stage1, (const void* q, int64_t q_stride_tok, int64_t q_strid
 // only launch.
 // ---------------------------------------------------------------------------
 namespace deft {
+// The device copy of the tree as the kernels take it; false: a count out of range or a null array (every caller reports that under
+// its own name, with what else it needs).
+static bool make_tree_dev(TreeDev& t, int n_nodes, int nq, int nqw, const int32_t* node_start, int32_t* node_len, const int32_t* node_cap,
+                          const uint64_t* refs, const int32_t* leaf_node, int32_t* slots) {
+    t = TreeDev{n_nodes, nq, nqw, node_start, node_len, node_cap, reinterpret_cast<const unsigned long long*>(refs), leaf_node, slots};
+    return n_nodes > 0 && nq >= 0 && nqw >= 1 && node_start && node_len && node_cap && refs && leaf_node && slots;
+}
 static TreeScratch tree_scratch_view(void* base, int n, int nqw, int nbp_cap, size_t* bytes) {
     TreeScratch s;
     char* p = static_cast<char*>(base);
@@ -2104,12 +1785,11 @@ int deft_tree_dev_advance(int n_nodes, int nq, int nqw, const int32_t* node_star
                           const uint64_t* refs, const int32_t* leaf_node, int32_t* slots, const int32_t* cache_loc,
                           void* scratch, void* stream) {
     if (nq == 0) return DEFT_OK;
-    if (n_nodes <= 0 || nq < 0 || nqw < 1 || !node_start || !node_len || !node_cap || !refs || !leaf_node || !slots || !cache_loc ||
-        !scratch) {
+    TreeDev t;
+    if (!make_tree_dev(t, n_nodes, nq, nqw, node_start, node_len, node_cap, refs, leaf_node, slots) || !cache_loc || !scratch) {
         set_error("deft_tree_dev_advance: bad arguments (nodes=%d nq=%d)", n_nodes, nq);
         return DEFT_EINVAL;
     }
-    TreeDev t{n_nodes, nq, nqw, node_start, node_len, node_cap, reinterpret_cast<const unsigned long long*>(refs), leaf_node, slots};
     hipLaunchKernelGGL(tree_advance_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), t,
                        cache_loc, static_cast<int32_t*>(scratch) + TREE_ERR);
     return check_launch("tree advance launch");
@@ -2120,11 +1800,11 @@ int deft_tree_dev_advance(int n_nodes, int nq, int nqw, const int32_t* node_star
 int deft_tree_dev_apply_ops(int n_nodes, int nq, int nqw, const int32_t* node_start, int32_t* node_len, const int32_t* node_cap,
                             const uint64_t* refs, const int32_t* leaf_node, int32_t* slots, const int32_t* ops, void* scratch,
                             void* stream) {
-    if (n_nodes <= 0 || nq < 0 || nqw < 1 || !node_start || !node_len || !node_cap || !refs || !leaf_node || !slots || !ops || !scratch) {
+    TreeDev t;
+    if (!make_tree_dev(t, n_nodes, nq, nqw, node_start, node_len, node_cap, refs, leaf_node, slots) || !ops || !scratch) {
         set_error("deft_tree_dev_apply_ops: bad arguments (nodes=%d nq=%d)", n_nodes, nq);
         return DEFT_EINVAL;
     }
-    TreeDev t{n_nodes, nq, nqw, node_start, node_len, node_cap, reinterpret_cast<const unsigned long long*>(refs), leaf_node, slots};
     hipLaunchKernelGGL(tree_ops_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), t, ops,
                        static_cast<int32_t*>(scratch) + TREE_ERR);
     return check_launch("tree ops launch");
@@ -2137,8 +1817,8 @@ static int tree_dev_build_md_impl(int n_nodes, int nq, int nqw, const int32_t* n
                            int64_t* block_q, int64_t* block_q_cnts, int64_t* block_q_offset, int64_t* block_bitmasks,
                            int64_t* block_kv, int64_t* block_lens, const int32_t* advance_loc, const int32_t* ops, PageWrite pw,
                            void* stream) {
-    if (n_nodes <= 0 || nq < 0 || nqw < 1 || nbp_cap < 0 || !node_start || !node_len || !node_cap || !refs || !leaf_node || !slots ||
-        !scratch) {
+    TreeDev t;
+    if (!make_tree_dev(t, n_nodes, nq, nqw, node_start, node_len, node_cap, refs, leaf_node, slots) || nbp_cap < 0 || !scratch) {
         set_error("deft_tree_dev_build_md: bad arguments (nodes=%d nq=%d)", n_nodes, nq);
         return DEFT_EINVAL;
     }
@@ -2161,7 +1841,6 @@ static int tree_dev_build_md_impl(int n_nodes, int nq, int nqw, const int32_t* n
         return DEFT_EWORKSPACE;
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
-    TreeDev t{n_nodes, nq, nqw, node_start, node_len, node_cap, reinterpret_cast<const unsigned long long*>(refs), leaf_node, slots};
     TreeMdOut o{node_q, node_kv, node_q_len, node_kv_len, node_q_offset, node_kv_offset,
                 block_q, block_q_cnts, block_q_offset, block_bitmasks, block_kv, block_lens};
     // node tables in LDS when the tree fits: 6 x (n + 1) words + one per block
@@ -2288,73 +1967,28 @@ int deft_flatten_build_plan_window(int64_t* block_q, int64_t* block_q_cnts, int6
                                    int64_t* block_kv, int64_t* block_lens, int NB, int P, int32_t* dims, int nq, int max_q_len,
                                    int win_tiles, int32_t* win_tab, int Hq, int Hkv, int64_t q_stride_tok, int64_t q_stride_head,
                                    int64_t kv_stride_slot, void* plan, size_t plan_bytes, void* stream) {
-    if (NB <= 0 || P <= 0 || !plan || !dims || !win_tab || win_tiles < 1 || !deft_window_supported(nq, max_q_len, Hq, Hkv) || !block_q ||
-        !block_q_cnts || !block_q_offset || !block_bitmasks || !block_kv || !block_lens) {
+    const FlattenMd md{block_q, block_q_cnts, block_q_offset, block_bitmasks, block_kv, block_lens, NB, P};
+    const WindowArgs win{dims, nq, max_q_len, win_tiles, win_tab};
+    if (NB <= 0 || P <= 0 || !md.ok() || !plan || !win.ok(Hq, Hkv)) {
         set_error("bad window plan arguments (NB=%d P=%d nq=%d max_q_len=%d tiles=%d)", NB, P, nq, max_q_len, win_tiles);
         return DEFT_EINVAL;
     }
-    const PlanView pv = plan_view(plan, flatten_unit_cap(NB, Hq / Hkv), P);
-    if (plan_bytes < pv.bytes) {
-        set_error("plan buffer too small: %zu < %zu", plan_bytes, pv.bytes);
-        return DEFT_EWORKSPACE;
-    }
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    TreeMdOut o{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, block_q, block_q_cnts, block_q_offset, block_bitmasks, block_kv, block_lens};
-    hipLaunchKernelGGL(window_blocks_kernel, dim3(1), dim3(256), 0, st, o, dims, nq, max_q_len, win_tiles, TILE, NB, P);
-    int rc = check_launch("window blocks launch");
-    if (rc) return rc;
-    Stage1Params p{};
-    p.block_q = block_q;
-    p.block_q_cnts = block_q_cnts;
-    p.block_q_offset = block_q_offset;
-    p.block_bitmasks = block_bitmasks;
-    p.block_kv = block_kv;
-    p.block_lens = block_lens;
-    p.rows = P;
-    p.G = Hq / Hkv;
-    p.Hkv = Hkv;
-    p.q_st = q_stride_tok;
-    p.q_sh = q_stride_head;
-    p.kv_ss = kv_stride_slot;
-    return launch_plan(p, NB, pv, AppendArgs(), st, dims, win_tiles, win_tab);
+    return flatten_build_plan_impl(md, plan_geometry(Hq, Hkv, q_stride_tok, q_stride_head, kv_stride_slot), AppendArgs(), plan, plan_bytes,
+                                   stream, dims, &win);
 }
 
 int deft_node_build_plan_window(int64_t* node_kv, int64_t* node_kv_offset, int64_t* node_kv_len, int64_t* node_q,
                                 int64_t* node_q_offset, int64_t* node_q_len, int NE, int P, int64_t total_kv, int32_t* dims, int nq,
                                 int max_q_len, int win_tiles, int32_t* win_tab, int Hq, int Hkv, int64_t q_stride_tok,
                                 int64_t q_stride_head, int64_t kv_stride_slot, void* plan, size_t plan_bytes, void* stream) {
-    if (NE <= 0 || P <= 0 || total_kv <= 0 || total_kv > 0x7fffffffLL || !plan || !dims || !win_tab || win_tiles < 1 ||
-        !deft_window_supported(nq, max_q_len, Hq, Hkv) || !node_kv || !node_kv_offset || !node_kv_len || !node_q || !node_q_offset ||
-        !node_q_len) {
+    const NodeMd md{node_kv, node_kv_offset, node_kv_len, node_q, node_q_offset, node_q_len, NE, P, total_kv, 0};
+    const WindowArgs win{dims, nq, max_q_len, win_tiles, win_tab};
+    if (NE <= 0 || P <= 0 || total_kv <= 0 || !md.ok() || !plan || !win.ok(Hq, Hkv)) {
         set_error("bad window plan arguments (NE=%d P=%d total_kv=%lld nq=%d)", NE, P, (long long)total_kv, nq);
         return DEFT_EINVAL;
     }
-    const int64_t tiles = node_max_tiles(NE, total_kv);
-    const int64_t rows = tiles * node_rows_per_tile(P);
-    const PlanView pv = plan_view(plan, tiles * (Hq / Hkv), rows);
-    if (plan_bytes < pv.bytes) {
-        set_error("plan buffer too small: %zu < %zu", plan_bytes, pv.bytes);
-        return DEFT_EWORKSPACE;
-    }
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    TreeMdOut o{node_q, node_kv, node_q_len, node_kv_len, node_q_offset, node_kv_offset, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    hipLaunchKernelGGL(window_entries_kernel, dim3(1), dim3(256), 0, st, o, dims, nq, max_q_len, win_tiles, NE, P, (int)total_kv);
-    int rc = check_launch("window entries launch");
-    if (rc) return rc;
-    Stage1Params p{};
-    p.node_kv = node_kv;
-    p.node_kv_offset = node_kv_offset;
-    p.node_kv_len = node_kv_len;
-    p.node_q = node_q;
-    p.node_q_offset = node_q_offset;
-    p.node_q_len = node_q_len;
-    p.rows = rows;
-    p.G = Hq / Hkv;
-    p.Hkv = Hkv;
-    p.q_st = q_stride_tok;
-    p.q_sh = q_stride_head;
-    p.kv_ss = kv_stride_slot;
-    return launch_node_plan(p, NE, rows, pv, AppendArgs(), st, 0, dims, win_tiles, win_tab);
+    return node_build_plan_impl(md, plan_geometry(Hq, Hkv, q_stride_tok, q_stride_head, kv_stride_slot), nullptr, 0, 0, plan, plan_bytes, stream,
+                                dims, &win);
 }
 
 int deft_window_patch(int n_nodes, int nq, int nqw, const int32_t* node_start, int32_t* node_len, const int32_t* node_cap,
@@ -2363,8 +1997,9 @@ int deft_window_patch(int n_nodes, int nq, int nqw, const int32_t* node_start, i
                       const int32_t* patch, const int32_t* win_tab, void* plan, int max_q_len, int win_tiles, int Hq, int Hkv,
                       int64_t kv_stride_slot, int64_t new_stride_tok, void* scratch, const void* fetch_ring, int fetch_slot_bytes,
                       int fetch_ring_n, void* fetch_dst, int32_t* fetch_counter, void* stream) {
-    if (n_nodes <= 0 || nq <= 0 || nqw < 1 || !node_start || !node_len || !node_cap || !refs || !leaf_node || !slots || !cache_loc ||
-        !patch || !win_tab || !plan || !scratch || win_tiles < 1 || !deft_window_supported(nq, max_q_len, Hq, Hkv)) {
+    TreeDev t;
+    if (!make_tree_dev(t, n_nodes, nq, nqw, node_start, node_len, node_cap, refs, leaf_node, slots) || nq <= 0 || !cache_loc || !patch ||
+        !win_tab || !plan || !scratch || win_tiles < 1 || !deft_window_supported(nq, max_q_len, Hq, Hkv)) {
         set_error("deft_window_patch: bad arguments (nodes=%d nq=%d tiles=%d)", n_nodes, nq, win_tiles);
         return DEFT_EINVAL;
     }
@@ -2372,7 +2007,6 @@ int deft_window_patch(int n_nodes, int nq, int nqw, const int32_t* node_start, i
         set_error("deft_window_patch: the page-table write needs rows, cols and a row stride");
         return DEFT_EINVAL;
     }
-    TreeDev t{n_nodes, nq, nqw, node_start, node_len, node_cap, reinterpret_cast<const unsigned long long*>(refs), leaf_node, slots};
     WindowPatch w{ops, cache_loc, patch, win_tab, static_cast<char*>(plan) + PLAN_HDR, static_cast<int32_t*>(scratch) + TREE_ERR,
                   static_cast<const int32_t*>(scratch) + WIN_DIM_PAD, max_q_len, Hq / Hkv, win_tiles, kv_stride_slot, new_stride_tok * 2};
     if (fetch_ring && (!fetch_dst || !fetch_counter || fetch_slot_bytes < 32 || fetch_slot_bytes % 16 || fetch_ring_n < 1)) {
