@@ -13,6 +13,16 @@ from .forward_mode import ForwardMode, InputMetadata, forward_mode_from_cli  # n
 from .memory_pool import ReqToTokenPool, TokenToKVPool  # noqa: F401
 from .rotary_embedding import RotaryEmbedding, get_rope  # noqa: F401
 from .session import DecodeSession, FlattenDecodeSession  # noqa: F401
+from .states import (  # noqa: F401
+    cached_prefix_blocks,
+    context_attention_fwd_lse,
+    flatten_append_attention_lse,
+    merge_attention_states,
+    node_append_attention_lse,
+    prefill_with_cached_prefix,
+    tree_attention_fwd_lse,
+    tree_attention_subtree_fwd_lse,
+)
 from .token_attention import token_attention_fwd  # noqa: F401
 from .tree_attention import kv_append, tree_attention_fwd, tree_attention_subtree_fwd  # noqa: F401
 from .tree_cache import (  # noqa: F401

@@ -120,6 +120,29 @@ for _f in ELEM_ENTRY_POINTS:
         getattr(lib, _f + "_bf16").argtypes = getattr(lib, _f + "_f16").argtypes
         getattr(lib, _f + "_bf16").restype = C.c_int
 
+# Attention states (deft_amd/states.py): the *_lse siblings take `lse, lse_stride_tok, lse_stride_head` behind the out strides.  Kept
+# apart from ELEM_ENTRY_POINTS, which names the entry points of the plain surface.
+_LSE = [_vp, _i64, _i64]
+# Their names carry the element type INSIDE ("{}" = _f16 / _bf16): deft_flatten_decode_f16_lse is the _lse form of deft_flatten_decode_f16.
+STATE_ENTRY_POINTS = ("deft_flatten_decode{}_lse", "deft_flatten_decode_append{}_lse", "deft_node_decode{}_lse", "deft_node_decode_append{}_lse",
+                      "deft_prefill{}_lse", "deft_merge{}_states")
+
+
+def _with_lse(argtypes, at):
+    return list(argtypes[:at]) + _LSE + list(argtypes[at:])
+
+
+for _f in ("deft_flatten_decode", "deft_flatten_decode_append", "deft_node_decode", "deft_node_decode_append"):
+    _plain = getattr(lib, _f + "_f16").argtypes
+    for _s in ("_f16", "_bf16"):
+        getattr(lib, _f + _s + "_lse").argtypes = _with_lse(_plain, len(_QKV + _OUT))
+        getattr(lib, _f + _s + "_lse").restype = C.c_int
+for _s in ("_f16", "_bf16"):
+    getattr(lib, "deft_prefill" + _s + "_lse").argtypes = _with_lse(lib.deft_prefill_f16.argtypes, 12)
+    getattr(lib, "deft_prefill" + _s + "_lse").restype = C.c_int
+    getattr(lib, "deft_merge" + _s + "_states").argtypes = [_vp, _i64, _i64] * 6 + [_i32, _i32, _i32, _vp]
+    getattr(lib, "deft_merge" + _s + "_states").restype = C.c_int
+
 _SUFFIX = {torch.float16: "_f16", torch.bfloat16: "_bf16"}
 ELEM_DTYPES = tuple(_SUFFIX)
 
@@ -145,8 +168,9 @@ def same_elem_dtype(**tensors) -> torch.dtype:
 
 
 def entry(name: str, dtype):
-    """(function, its name) of data entry point `name` ("deft_flatten_decode", ...) for an element type."""
-    full = name + elem_suffix(dtype)
+    """(function, its name) of data entry point `name` ("deft_flatten_decode", ...) for an element type; a "{}" in `name` is where
+    the suffix goes (STATE_ENTRY_POINTS)."""
+    full = name.format(elem_suffix(dtype)) if "{}" in name else name + elem_suffix(dtype)
     if not hasattr(lib, full):
         raise DeftLibraryError(f"{LIB_PATH} does not export {full}: a build from before the bfloat16 entry points")
     return getattr(lib, full), full
@@ -224,7 +248,7 @@ EXPORTED = (
     "deft_prefill_f16", "deft_rope_qk_f16", "deft_seq_plan_bytes", "deft_seq_workspace_bytes", "deft_seq_build_plan", "deft_seq_decode_f16", "deft_seq_decode_append_f16",
     "deft_kv_append_f16", "deft_probe_stream_read", "deft_md_build", "deft_md_sizes", "deft_md_fetch", "deft_md_free",
     "deft_tree_create",
-) + tuple(_f + "_bf16" for _f in ELEM_ENTRY_POINTS) + tuple(_TREE_FUNCS)
+) + tuple(_f + "_bf16" for _f in ELEM_ENTRY_POINTS) + tuple(_f.format(_s) for _f in STATE_ENTRY_POINTS for _s in ("_f16", "_bf16")) + tuple(_TREE_FUNCS)
 
 _ERR_NAMES = {-1: "DEFT_EINVAL", -2: "DEFT_EUNSUPPORTED", -3: "DEFT_EHIP", -4: "DEFT_EWORKSPACE"}
 

@@ -20,6 +20,11 @@ struct Tensors {
     int64_t o_st, o_sh;
     int nq, Hq, Hkv, D;
     float scale;
+    // the *_lse entry points: one fp32 log-sum-exp per (query, head) at lse[q * lse_st + hq * lse_sh] (strides in elements);
+    // null and 0 in a plain call
+    float* lse = nullptr;
+    int64_t lse_st = 0, lse_sh = 0;
+    bool lse_call = false;  // an *_lse entry point: a null lse is an error there, not "no log-sum-exp"
 
     int G() const { return Hq / Hkv; }
     bool heads_ok() const { return Hq > 0 && Hkv > 0 && Hq % Hkv == 0; }
@@ -42,6 +47,14 @@ struct Tensors {
         }
         if ((reinterpret_cast<uintptr_t>(out) & 3u) || (o_st % 2) || (o_sh % 2)) {
             set_error("out rows must be 4-byte aligned");
+            return DEFT_EINVAL;
+        }
+        if (lse_call && !lse) {
+            set_error("null lse (the plain entry point returns no log-sum-exp)");
+            return DEFT_EINVAL;
+        }
+        if (reinterpret_cast<uintptr_t>(lse) & 3u) {
+            set_error("lse must be 4-byte aligned");
             return DEFT_EINVAL;
         }
         return DEFT_OK;

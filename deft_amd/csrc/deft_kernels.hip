@@ -391,11 +391,13 @@ __global__ __launch_bounds__(256) void node_prep_kernel(const int64_t* node_kv_o
 // that a head is merged on the XCD whose L2 holds its partial rows.
 // ---------------------------------------------------------------------------
 constexpr int MERGE_LIST_CAP = 4096;  // row ids per wave in LDS; longer lists are merged window by window
-template <class T, int D>
+// LSE: the row's log-sum-exp goes to lse[q * lse_st + hq * lse_sh] as well (merge_finish); the plain instantiation ignores the
+// three trailing arguments.
+template <class T, int D, bool LSE = false>
 __global__ __launch_bounds__(256) void merge_kernel(const float* partial_o, const float* partial_lse, const int32_t* row_q,
                                                      int64_t rows, e16* out, int64_t o_st, int64_t o_sh, int Hq, int cap,
                                                      int lists, const int32_t* qoff, const int32_t* qlist, const int32_t* qinl,
-                                                     int nq_total, int hgroup) {
+                                                     int nq_total, int hgroup, float* lse, int64_t lse_st, int64_t lse_sh) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;  // (uniform: buffer descriptors stay in SGPRs)
     // EXPERIMENT (XCD alignment): a workgroup = one HEAD x four queries, head fastest in the grid: workgroup b runs on XCD b % 8 = the
@@ -412,6 +414,7 @@ __global__ __launch_bounds__(256) void merge_kernel(const float* partial_o, cons
     const int q = blockIdx.y * 4 + w;
     if (q >= nq_total) return;
     e16* out_q = out + (int64_t)q * o_st;
+    float* lse_q = LSE ? lse + (int64_t)q * lse_st : nullptr;
     int* list = reinterpret_cast<int*>(smem) + w * cap;
 #ifdef DEFT_EXPERIMENTS
     if (lists >= 2) {  // TIMING ONLY (wrong results): row ids computed, not loaded -- what a merge without its first dependent round trip costs
@@ -428,22 +431,22 @@ __global__ __launch_bounds__(256) void merge_kernel(const float* partial_o, cons
         if (n <= 15 && n <= cap) {
             if (lane >= 1 && lane <= n) list[lane - 1] = mine;
             __builtin_amdgcn_wave_barrier();
-            merge_heads_wave<T, D, 0, 1>(partial_o, partial_lse, row_q, rows, q, hq, 1, Hq, list, cap, n, out_q, o_sh, lane);
+            merge_heads_wave<T, D, 0, 1, LSE>(partial_o, partial_lse, row_q, rows, q, hq, 1, Hq, list, cap, n, out_q, o_sh, lane, lse_q, lse_sh);
         } else if (n <= cap) {  // a longer list: the query's stretch of qlist, staged in LDS with one coalesced read
             const int o = qoff[q];
             for (int j = lane; j < n; j += 64) list[j] = qlist[o + j];
             __builtin_amdgcn_wave_barrier();
-            merge_heads_wave<T, D, 0, 1>(partial_o, partial_lse, row_q, rows, q, hq, 1, Hq, list, cap, n, out_q, o_sh, lane);
+            merge_heads_wave<T, D, 0, 1, LSE>(partial_o, partial_lse, row_q, rows, q, hq, 1, Hq, list, cap, n, out_q, o_sh, lane, lse_q, lse_sh);
         } else {  // longer than the LDS area: read in place
             const int o = qoff[q];
-            merge_heads_wave<T, D, 0, 1>(partial_o, partial_lse, row_q, rows, q, hq, 1, Hq, const_cast<int*>(qlist) + o, n, n, out_q, o_sh, lane);
+            merge_heads_wave<T, D, 0, 1, LSE>(partial_o, partial_lse, row_q, rows, q, hq, 1, Hq, const_cast<int*>(qlist) + o, n, n, out_q, o_sh, lane, lse_q, lse_sh);
         }
         return;
     }
     int have = scan_rows_wave(row_q, 0, rows < cap ? rows : cap, q, list, cap, lane);
     if (rows > cap) have = -1;
     __builtin_amdgcn_wave_barrier();
-    merge_heads_wave<T, D, 0, 1>(partial_o, partial_lse, row_q, rows, q, hq, 1, Hq, list, cap, have, out_q, o_sh, lane);
+    merge_heads_wave<T, D, 0, 1, LSE>(partial_o, partial_lse, row_q, rows, q, hq, 1, Hq, list, cap, have, out_q, o_sh, lane, lse_q, lse_sh);
 }
 
 // Long row lists (a long shared prefix under few queries: 64k tokens x 8 branches is 66 rows per query, and only
@@ -451,10 +454,11 @@ __global__ __launch_bounds__(256) void merge_kernel(const float* partial_o, cons
 // folding a quarter (merge_accumulate: 8 rows per round trip, so 66 rows cost 3 trips instead of 9), then one combine of the
 // four (m, L, acc) states through LDS.  Deterministic (the deal is a function of the list); its fp32 order differs from
 // merge_kernel's, so a launch uses one or the other as a function of its SHAPE only (launch_merge).
-template <class T, int D>
+template <class T, int D, bool LSE = false>
 __global__ __launch_bounds__(256) void merge_coop_kernel(const float* partial_o, const float* partial_lse, int64_t rows, e16* out,
                                                           int64_t o_st, int64_t o_sh, int cap, const int32_t* qoff,
-                                                          const int32_t* qlist, const int32_t* qinl, int Hq, int hgroup) {
+                                                          const int32_t* qlist, const int32_t* qinl, int Hq, int hgroup, float* lse,
+                                                          int64_t lse_st, int64_t lse_sh) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int LPR = D / 4;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -469,7 +473,8 @@ __global__ __launch_bounds__(256) void merge_coop_kernel(const float* partial_o,
         if (w == 0) {
             if (lane >= 1 && lane <= n) sub[lane - 1] = mine;
             __builtin_amdgcn_wave_barrier();
-            merge_heads_wave<T, D, 0, 1>(partial_o, partial_lse, nullptr, rows, q, hq, 1, hq + 1, sub, cap, n, out + (int64_t)q * o_st, o_sh, lane);
+            merge_heads_wave<T, D, 0, 1, LSE>(partial_o, partial_lse, nullptr, rows, q, hq, 1, hq + 1, sub, cap, n, out + (int64_t)q * o_st, o_sh, lane,
+                                              LSE ? lse + (int64_t)q * lse_st : nullptr, lse_sh);
         }
         return;
     }
@@ -519,6 +524,7 @@ __global__ __launch_bounds__(256) void merge_coop_kernel(const float* partial_o,
         const float inv = L > 0.f ? 1.f / L : 0.f;
         e16* dst = out + (int64_t)q * o_st + (int64_t)hq * o_sh;
         store_row4<T>(dst + 4 * lane, acc[0] * inv, acc[1] * inv, acc[2] * inv, acc[3] * inv);
+        if (LSE && lane == 0) lse[(int64_t)q * lse_st + (int64_t)hq * lse_sh] = L > 0.f ? M + logf(L) : -INFINITY;
     }
 }
 
@@ -610,7 +616,7 @@ static int num_cus() {
     return d.cus;
 }
 enum : unsigned { ATTR_NP = 4,  // (bits 0-1, 8-11: the head_dim 64 / 32 / 16 kernels)
-                  ATTR_UNITS = 8, ATTR_NODE_UNITS = 16, ATTR_PREFILL = 32, ATTR_TREE = 64, ATTR_NP_ROPE = 128, ATTR_NP_T = 8192, ATTR_NP_ROPE_T = 16384, ATTR_NP_HD2 = 32768, ATTR_NP_HD2_T = 65536, ATTR_PREFILL_64 = 1u << 17, ATTR_NP_DYN = 1u << 18, ATTR_NP_ROPE_DYN = 1u << 19, ATTR_NP_HD2_DYN = 1u << 20 };
+                  ATTR_UNITS = 8, ATTR_NODE_UNITS = 16, ATTR_PREFILL = 32, ATTR_TREE = 64, ATTR_NP_ROPE = 128, ATTR_NP_T = 8192, ATTR_NP_ROPE_T = 16384, ATTR_NP_HD2 = 32768, ATTR_NP_HD2_T = 65536, ATTR_PREFILL_64 = 1u << 17, ATTR_NP_DYN = 1u << 18, ATTR_NP_ROPE_DYN = 1u << 19, ATTR_NP_HD2_DYN = 1u << 20, ATTR_PREFILL_LSE = 1u << 21, ATTR_PREFILL_64_LSE = 1u << 22 };
 template <class T>
 constexpr uint64_t attr_bit(unsigned bit) { return std::is_same<T, BF16>::value ? (uint64_t)bit << 32 : (uint64_t)bit; }
 static int raise_lds(const void* fn, int bytes, uint64_t bit, const char* what) {  // idempotent; races are harmless
@@ -652,6 +658,7 @@ static int launch_stage1_d64(int D, const Stage1Params& p, int64_t tiles, hipStr
 
 }  // namespace deft
 #include "call.h"  // Tensors, FlattenMd, NodeMd, AppendArgs, Scratch: one decode call, described and checked once
+#include "states.h"  // merge of two attention states (o, lse): the kernel and its host half
 namespace deft {
 
 static UnitList unit_list(const PlanView& pv) {
@@ -853,16 +860,20 @@ static int launch_stage1_np(const Stage1Params& p, int64_t unit_cap, const PlanV
     return check_launch("stage1 np launch");
 }
 
-template <class T>
-static int launch_merge(int D, const Workspace& ws, const PlanView* pv, const int32_t* row_q, int64_t rows, void* out,
-                        int64_t o_st, int64_t o_sh, int nq, int Hq, int hgroup, hipStream_t stream) {
+// lse != null: the LSE instantiations, which store every row's log-sum-exp next to its output (the *_lse entry points).
+template <class T, bool LSE>
+static int launch_merge_t(int D, const Workspace& ws, const PlanView* pv, const int32_t* row_q, int64_t rows, void* out,
+                          int64_t o_st, int64_t o_sh, int nq, int Hq, int hgroup, hipStream_t stream, float* lse, int64_t lse_st,
+                          int64_t lse_sh) {
     if (nq <= 0) return DEFT_OK;
     const int cap = (int)std::min<int64_t>(std::max<int64_t>(rows, 64), MERGE_LIST_CAP);
     const size_t lds = sizeof(int) * 4 * (size_t)cap;
     if (hgroup <= 0 || Hq % hgroup) hgroup = 1;
     dim3 grid((unsigned)Hq, (unsigned)((nq + 3) / 4));
     // the plan's per-query row lists exist iff its row count fits the histogram kernel (launch_qrows): known on the host
-    int lists = pv && pv->rows > 0 && pv->rows <= QROWS_MAX ? 1 : 0;
+    // -- and they are indexed by query up to `rows` (qrows_*_kernel): a call with more queries than partial rows, where some query
+    // has no row at all (one half of a split tree, states.h), scans row_q instead and finishes such a query as (0, -inf)
+    int lists = pv && pv->rows > 0 && pv->rows <= QROWS_MAX && nq <= pv->rows ? 1 : 0;
 #ifdef DEFT_EXPERIMENTS
     if (const int fake = knob("DEFT_MERGE_FAKE", 0)) lists = 1 + fake;  // (timing experiment: `fake` computed row ids per query)
 #endif
@@ -876,19 +887,27 @@ static int launch_merge(int D, const Workspace& ws, const PlanView* pv, const in
     if (D == 128 && lists && nq <= 16 && (int64_t)nq * Hq <= 1024) {
         const int ccap = (int)std::min<int64_t>(std::max<int64_t>(rows / 4 + 2, 16), MERGE_LIST_CAP);  // (>= 8: the single-wave path stages up to 8 rows)
         const size_t clds = sizeof(int) * 4 * (size_t)ccap + sizeof(float) * (4 * 128 + 8);
-        hipLaunchKernelGGL((merge_coop_kernel<T, 128>), dim3((unsigned)Hq, (unsigned)nq), dim3(256), clds, stream, ws.partial_o,
-                           ws.partial_lse, rows, static_cast<e16*>(out), o_st, o_sh, ccap, qoff, qlist, qinl, Hq, hgroup);
+        hipLaunchKernelGGL((merge_coop_kernel<T, 128, LSE>), dim3((unsigned)Hq, (unsigned)nq), dim3(256), clds, stream, ws.partial_o,
+                           ws.partial_lse, rows, static_cast<e16*>(out), o_st, o_sh, ccap, qoff, qlist, qinl, Hq, hgroup, lse, lse_st,
+                           lse_sh);
         return check_launch("merge (cooperative) launch");
     }
 #define DEFT_MERGE_LAUNCH(DD)                                                                                              \
-    hipLaunchKernelGGL((merge_kernel<T, DD>), grid, dim3(256), lds, stream, ws.partial_o, ws.partial_lse, row_q, rows,         \
-                       static_cast<e16*>(out), o_st, o_sh, Hq, cap, lists, qoff, qlist, qinl, nq, hgroup)
+    hipLaunchKernelGGL((merge_kernel<T, DD, LSE>), grid, dim3(256), lds, stream, ws.partial_o, ws.partial_lse, row_q, rows,    \
+                       static_cast<e16*>(out), o_st, o_sh, Hq, cap, lists, qoff, qlist, qinl, nq, hgroup, lse, lse_st, lse_sh)
     if (D == 128) DEFT_MERGE_LAUNCH(128);
     else if (D == 64) DEFT_MERGE_LAUNCH(64);
     else if (D == 32) DEFT_MERGE_LAUNCH(32);
     else DEFT_MERGE_LAUNCH(16);
 #undef DEFT_MERGE_LAUNCH
     return check_launch("merge launch");
+}
+template <class T>
+static int launch_merge(int D, const Workspace& ws, const PlanView* pv, const int32_t* row_q, int64_t rows, void* out,
+                        int64_t o_st, int64_t o_sh, int nq, int Hq, int hgroup, hipStream_t stream, float* lse = nullptr,
+                        int64_t lse_st = 0, int64_t lse_sh = 0) {
+    return lse ? launch_merge_t<T, true>(D, ws, pv, row_q, rows, out, o_st, o_sh, nq, Hq, hgroup, stream, lse, lse_st, lse_sh)
+               : launch_merge_t<T, false>(D, ws, pv, row_q, rows, out, o_st, o_sh, nq, Hq, hgroup, stream, nullptr, 0, 0);
 }
 
 }  // namespace deft
@@ -1101,7 +1120,7 @@ static int flatten_decode_impl(const Tensors& t, const FlattenMd& md, const Appe
     rc = flatten_stage1_impl<T>(t, md, ap, sc, &ws, &row_q, &pv);
     if (rc) return rc;
     return launch_merge<T>(t.D, ws, pv.hdr ? &pv : nullptr, row_q, md.P, t.out, t.o_st, t.o_sh, t.nq, t.Hq,
-                        t.G() * (hd2_geometry(t.D, t.Hkv, t.kv_sh) && !ap.cos_sin ? 2 : 1), sc.st());
+                        t.G() * (hd2_geometry(t.D, t.Hkv, t.kv_sh) && !ap.cos_sin ? 2 : 1), sc.st(), t.lse, t.lse_st, t.lse_sh);
 }
 
 extern "C" {
@@ -1246,7 +1265,7 @@ static int node_decode_impl(const Tensors& t, const NodeMd& md, const AppendArgs
         }
         rc = launch_stage1_np<T>(p, tiles * G, pv, ap, st, t.nq, /*reread=*/seq, hd2);
         if (rc) return rc;
-        return launch_merge<T>(t.D, ws, &pv, pv.row_q, rows, t.out, t.o_st, t.o_sh, t.nq, t.Hq, G * (hd2 ? 2 : 1), st);
+        return launch_merge<T>(t.D, ws, &pv, pv.row_q, rows, t.out, t.o_st, t.o_sh, t.nq, t.Hq, G * (hd2 ? 2 : 1), st, t.lse, t.lse_st, t.lse_sh);
     }
     // tile-per-workgroup form (head_dim 64)
     rc = append_first(t, ap, sc.stream);
@@ -1263,7 +1282,7 @@ static int node_decode_impl(const Tensors& t, const NodeMd& md, const AppendArgs
     p.desc = ws.desc;
     rc = launch_stage1_d64<T, 1>(t.D, p, tiles, st);
     if (rc) return rc;
-    return launch_merge<T>(t.D, ws, nullptr, ws.row_q, rows, t.out, t.o_st, t.o_sh, t.nq, t.Hq, 1, st);
+    return launch_merge<T>(t.D, ws, nullptr, ws.row_q, rows, t.out, t.o_st, t.o_sh, t.nq, t.Hq, 1, st, t.lse, t.lse_st, t.lse_sh);
 }
 
 static int kv_append_impl(void* k_base, void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head,
@@ -1539,13 +1558,47 @@ extern "C" int deft_rope_gather_rows(const int64_t* positions, const float* cos_
 // Causal prefill attention (prefill.h): context_attention_fwd
 // (DeFT/deft/layers/attention/context_flashattention_nopad.py:130-195)
 // ---------------------------------------------------------------------------
+// lse_call: deft_prefill_*_lse -- the LSE instantiations, which store every (token, head)'s log-sum-exp as well; the plain entry
+// point passes null.
+template <class T, bool LSE>
+static int prefill_launch(const deft::PrefillParams& p, int D, hipStream_t stream) {
+    using namespace deft;
+    if (D == 128) {
+        const int rc = raise_lds(reinterpret_cast<const void*>(&prefill_kernel<T, 128, LSE>), PrefillSmem<128>::BYTES,
+                                 attr_bit<T>(LSE ? ATTR_PREFILL_LSE : ATTR_PREFILL), "prefill");
+        if (rc) return rc;
+    } else if (D == 64) {
+        const int rc = raise_lds(reinterpret_cast<const void*>(&prefill_kernel<T, 64, LSE>), PrefillSmem<64>::BYTES,
+                                 attr_bit<T>(LSE ? ATTR_PREFILL_64_LSE : ATTR_PREFILL_64), "prefill (head_dim 64)");
+        if (rc) return rc;
+    }
+    const dim3 grid((unsigned)((int64_t)p.nblk * p.Hq * p.batch));
+    if (D == 128) hipLaunchKernelGGL((prefill_kernel<T, 128, LSE>), grid, dim3(512), PrefillSmem<128>::BYTES, stream, p);
+    else if (D == 64) hipLaunchKernelGGL((prefill_kernel<T, 64, LSE>), grid, dim3(512), PrefillSmem<64>::BYTES, stream, p);
+    else {  // head_dim 32 / 16: a wave per (token, head)
+        const dim3 g2((unsigned)((((int64_t)p.nblk * 256 + 3) / 4) * p.batch), (unsigned)p.Hq);
+        if (D == 32) hipLaunchKernelGGL((prefill_small_kernel<T, 32, LSE>), g2, dim3(256), 0, stream, p);
+        else hipLaunchKernelGGL((prefill_small_kernel<T, 16, LSE>), g2, dim3(256), 0, stream, p);
+    }
+    return check_launch("prefill launch");
+}
+
 template <class T>
 static int prefill_t(const void* q, int64_t q_stride_tok, int64_t q_stride_head, const void* k,
                      int64_t k_stride_tok, int64_t k_stride_head, const void* v, int64_t v_stride_tok,
                      int64_t v_stride_head, void* out, int64_t o_stride_tok, int64_t o_stride_head,
                      const int32_t* b_start_loc, const int32_t* b_seq_len, int batch, int max_input_len, int Hq,
-                     int Hkv, int D, float scale, void* stream) {
+                     int Hkv, int D, float scale, void* stream, float* lse = nullptr, int64_t lse_stride_tok = 0,
+                     int64_t lse_stride_head = 0, bool lse_call = false) {
     using namespace deft;
+    if (lse_call && !lse) {  // (before the empty-batch return: a malformed call is refused whatever its size)
+        set_error("prefill: null lse (the plain entry point returns no log-sum-exp)");
+        return DEFT_EINVAL;
+    }
+    if (reinterpret_cast<uintptr_t>(lse) & 3u) {
+        set_error("prefill: lse must be 4-byte aligned");
+        return DEFT_EINVAL;
+    }
     if (batch == 0 || max_input_len == 0) return DEFT_OK;
     if (!q || !k || !v || !out || !b_start_loc || !b_seq_len || batch < 0 || max_input_len < 0 || Hq <= 0 || Hkv <= 0 ||
         Hq % Hkv) {
@@ -1561,13 +1614,6 @@ static int prefill_t(const void* q, int64_t q_stride_tok, int64_t q_stride_head,
         (o_stride_tok % 4) || (o_stride_head % 4)) {
         set_error("prefill: q/k/v rows must be 16-byte aligned, out rows 8-byte aligned");
         return DEFT_EINVAL;
-    }
-    if (D == 128) {
-        const int rc = raise_lds(reinterpret_cast<const void*>(&prefill_kernel<T, 128>), PrefillSmem<128>::BYTES, attr_bit<T>(ATTR_PREFILL), "prefill");
-        if (rc) return rc;
-    } else if (D == 64) {
-        const int rc = raise_lds(reinterpret_cast<const void*>(&prefill_kernel<T, 64>), PrefillSmem<64>::BYTES, attr_bit<T>(ATTR_PREFILL_64), "prefill (head_dim 64)");
-        if (rc) return rc;
     }
     PrefillParams p{};
     p.q = static_cast<const e16*>(q);
@@ -1590,19 +1636,14 @@ static int prefill_t(const void* q, int64_t q_stride_tok, int64_t q_stride_head,
     p.Hq = Hq;
     p.batch = batch;
     p.dbg = g_dbg;
+    p.lse = lse;
+    p.lse_st = lse_stride_tok;
+    p.lse_sh = lse_stride_head;
     if ((int64_t)p.nblk * Hq * batch > 0x7fffffffLL) {
         set_error("prefill grid too large (%d query blocks x %d heads x %d sequences)", p.nblk, Hq, batch);
         return DEFT_EINVAL;
     }
-    const dim3 grid((unsigned)((int64_t)p.nblk * Hq * batch));
-    if (D == 128) hipLaunchKernelGGL((prefill_kernel<T, 128>), grid, dim3(512), PrefillSmem<128>::BYTES, static_cast<hipStream_t>(stream), p);
-    else if (D == 64) hipLaunchKernelGGL((prefill_kernel<T, 64>), grid, dim3(512), PrefillSmem<64>::BYTES, static_cast<hipStream_t>(stream), p);
-    else {  // head_dim 32 / 16: a wave per (token, head)
-        const dim3 g2((unsigned)((((int64_t)p.nblk * 256 + 3) / 4) * batch), (unsigned)Hq);
-        if (D == 32) hipLaunchKernelGGL((prefill_small_kernel<T, 32>), g2, dim3(256), 0, static_cast<hipStream_t>(stream), p);
-        else hipLaunchKernelGGL((prefill_small_kernel<T, 16>), g2, dim3(256), 0, static_cast<hipStream_t>(stream), p);
-    }
-    return check_launch("prefill launch");
+    return lse ? prefill_launch<T, true>(p, D, static_cast<hipStream_t>(stream)) : prefill_launch<T, false>(p, D, static_cast<hipStream_t>(stream));
 }
 
 
@@ -1615,6 +1656,11 @@ static int prefill_t(const void* q, int64_t q_stride_tok, int64_t q_stride_head,
 #define DEFT_TWINS(name, params, ...)                                              \
     extern "C" int deft_##name##_f16 params { using T = F16; __VA_ARGS__ }         \
     extern "C" int deft_##name##_bf16 params { using T = BF16; __VA_ARGS__ }
+// ... and the entry points of the attention states (states.h), which carry the element type INSIDE the name -- deft_<op>_f16_lse is
+// "the _lse form of deft_<op>_f16", deft_merge_f16_states -- so that the *_f16 / *_bf16 names stay the twelve of the plain surface
+#define DEFT_STATE_TWINS(pre, post, params, ...)                                          \
+    extern "C" int deft_##pre##_f16##post params { using T = F16; __VA_ARGS__ }          \
+    extern "C" int deft_##pre##_bf16##post params { using T = BF16; __VA_ARGS__ }
 #define TENSORS \
     Tensors{q, q_stride_tok, q_stride_head, k_base, v_base, kv_stride_slot, kv_stride_head, out, o_stride_tok, o_stride_head, nq, Hq, Hkv, D, scale}
 #define FLATTEN_MD FlattenMd{block_q, block_q_cnts, block_q_offset, block_bitmasks, block_kv, block_lens, NB, P}
@@ -1685,6 +1731,62 @@ DEFT_TWINS(prefill, (const void* q, int64_t q_stride_tok, int64_t q_stride_head,
            { return prefill_t<T>(q, q_stride_tok, q_stride_head, k, k_stride_tok, k_stride_head, v, v_stride_tok,
                                  v_stride_head, out, o_stride_tok, o_stride_head, b_start_loc, b_seq_len, batch, max_input_len, Hq,
                                  Hkv, D, scale, stream); })
+// The *_lse twins of the five calls above: the plain sibling's parameter list with the log-sum-exp output behind the out strides,
+// the same *_impl behind them (Tensors carries lse to launch_merge / prefill_t, which pick the LSE instantiations).
+#define TENSORS_LSE                                                                                                                      \
+    Tensors{q, q_stride_tok, q_stride_head, k_base, v_base, kv_stride_slot, kv_stride_head, out, o_stride_tok, o_stride_head, nq, Hq, Hkv, D, \
+            scale, lse, lse_stride_tok, lse_stride_head, true}
+DEFT_STATE_TWINS(flatten_decode, _lse, (const void* q, int64_t q_stride_tok, int64_t q_stride_head, const void* k_base, const void*
+            v_base, int64_t kv_stride_slot, int64_t kv_stride_head, void* out, int64_t o_stride_tok, int64_t o_stride_head,
+            float* lse, int64_t lse_stride_tok, int64_t lse_stride_head,
+            const int64_t* block_q, const int64_t* block_q_cnts, const int64_t* block_q_offset, const int64_t* block_bitmasks,
+            const int64_t* block_kv, const int64_t* block_lens, int NB, int P, int nq, int Hq, int Hkv, int D, float scale,
+            const void* plan, void* workspace, size_t workspace_bytes, void* stream),
+           { return flatten_decode_impl<T>(TENSORS_LSE, FLATTEN_MD, AppendArgs(), SCRATCH); })
+DEFT_STATE_TWINS(flatten_decode_append, _lse, (const void* q, int64_t q_stride_tok, int64_t q_stride_head, void* k_base, void* v_base,
+            int64_t kv_stride_slot, int64_t kv_stride_head, void* out, int64_t o_stride_tok, int64_t o_stride_head,
+            float* lse, int64_t lse_stride_tok, int64_t lse_stride_head, const
+            int64_t* block_q, const int64_t* block_q_cnts, const int64_t* block_q_offset, const int64_t* block_bitmasks, const
+            int64_t* block_kv, const int64_t* block_lens, int NB, int P, int nq, int Hq, int Hkv, int D, float scale, const
+            int32_t* cache_loc, const void* k_new, const void* v_new, int64_t new_stride_tok, int n_new, const void* plan,
+            void* workspace, size_t workspace_bytes, void* stream), {
+    AppendArgs ap;
+    if (int rc = make_append(ap, APPEND)) return rc;
+    return flatten_decode_impl<T>(TENSORS_LSE, FLATTEN_MD, ap, SCRATCH);
+})
+DEFT_STATE_TWINS(node_decode, _lse, (const void* q, int64_t q_stride_tok, int64_t q_stride_head, const void* k_base, const void* v_base,
+            int64_t kv_stride_slot, int64_t kv_stride_head, void* out, int64_t o_stride_tok, int64_t o_stride_head,
+            float* lse, int64_t lse_stride_tok, int64_t lse_stride_head, const
+            int64_t* node_kv, const int64_t* node_kv_offset, const int64_t* node_kv_len, const int64_t* node_q, const int64_t*
+            node_q_offset, const int64_t* node_q_len, int NE, int P, int64_t total_kv, int nq, int Hq, int Hkv, int D, float
+            scale, const void* plan, void* workspace, size_t workspace_bytes, void* stream),
+           { return node_decode_impl<T>(TENSORS_LSE, NODE_MD, AppendArgs(), SCRATCH); })
+DEFT_STATE_TWINS(node_decode_append, _lse, (const void* q, int64_t q_stride_tok, int64_t q_stride_head, void* k_base, void* v_base,
+            int64_t kv_stride_slot, int64_t kv_stride_head, void* out, int64_t o_stride_tok, int64_t o_stride_head,
+            float* lse, int64_t lse_stride_tok, int64_t lse_stride_head, const
+            int64_t* node_kv, const int64_t* node_kv_offset, const int64_t* node_kv_len, const int64_t* node_q, const int64_t*
+            node_q_offset, const int64_t* node_q_len, int NE, int P, int64_t total_kv, int nq, int Hq, int Hkv, int D, float
+            scale, const int32_t* cache_loc, const void* k_new, const void* v_new, int64_t new_stride_tok, int n_new, const
+            void* plan, void* workspace, size_t workspace_bytes, void* stream), {
+    AppendArgs ap;
+    if (int rc = make_append(ap, APPEND)) return rc;
+    return node_decode_impl<T>(TENSORS_LSE, NODE_MD, ap, SCRATCH);
+})
+#undef TENSORS_LSE
+DEFT_STATE_TWINS(prefill, _lse, (const void* q, int64_t q_stride_tok, int64_t q_stride_head, const void* k, int64_t k_stride_tok, int64_t
+            k_stride_head, const void* v, int64_t v_stride_tok, int64_t v_stride_head, void* out, int64_t o_stride_tok,
+            int64_t o_stride_head, float* lse, int64_t lse_stride_tok, int64_t lse_stride_head, const int32_t* b_start_loc,
+            const int32_t* b_seq_len, int batch, int max_input_len, int Hq, int Hkv, int D, float scale, void* stream),
+           { return prefill_t<T>(q, q_stride_tok, q_stride_head, k, k_stride_tok, k_stride_head, v, v_stride_tok,
+                                 v_stride_head, out, o_stride_tok, o_stride_head, b_start_loc, b_seq_len, batch, max_input_len, Hq,
+                                 Hkv, D, scale, stream, lse, lse_stride_tok, lse_stride_head, true); })
+DEFT_STATE_TWINS(merge, _states, (const void* o_a, int64_t a_stride_tok, int64_t a_stride_head, const float* lse_a, int64_t lse_a_stride_tok,
+            int64_t lse_a_stride_head, const void* o_b, int64_t b_stride_tok, int64_t b_stride_head, const float* lse_b,
+            int64_t lse_b_stride_tok, int64_t lse_b_stride_head, void* out, int64_t o_stride_tok, int64_t o_stride_head,
+            float* lse_out, int64_t lse_out_stride_tok, int64_t lse_out_stride_head, int n, int Hq, int D, void* stream),
+           { return merge_states_t<T>(o_a, a_stride_tok, a_stride_head, lse_a, lse_a_stride_tok, lse_a_stride_head, o_b, b_stride_tok,
+                                      b_stride_head, lse_b, lse_b_stride_tok, lse_b_stride_head, out, o_stride_tok, o_stride_head,
+                                      lse_out, lse_out_stride_tok, lse_out_stride_head, n, Hq, D, stream); })
 DEFT_TWINS(rope_qk, (void* q, int64_t q_stride_tok, int64_t q_stride_head, int Hq, void* k, int64_t k_stride_tok, int64_t
             k_stride_head, int Hk, const int64_t* positions, const float* cos_sin_cache, int64_t cache_stride, int n, int D,
             int rotary_dim, int is_neox_style, void* stream),

@@ -126,9 +126,11 @@ __device__ __forceinline__ void store_row4(e16* dst, float x0, float x1, float x
     *reinterpret_cast<vec2*>(dst + 2) = hi;
 }
 
-// Sum the row groups of the wave and write the pair's output row (element type T, one rounding).
-template <class T, int D>
-__device__ inline void merge_finish(const MergeState& st, e16* dst, int lane) {
+// Sum the row groups of the wave and write the pair's output row (element type T, one rounding).  LSE: lane 0 also stores
+// the row's log-sum-exp m + log L (natural log, scale included; -inf for a row that saw nothing) -- the second half of the
+// row's attention STATE (states.h).  m and L are wave-uniform.
+template <class T, int D, bool LSE = false>
+__device__ inline void merge_finish(const MergeState& st, e16* dst, int lane, float* lse_dst = nullptr) {
     constexpr int LPR = D / 4;
     floatx4 a = st.acc;
 #pragma unroll
@@ -139,6 +141,7 @@ __device__ inline void merge_finish(const MergeState& st, e16* dst, int lane) {
         const float inv = st.L > 0.f ? 1.f / st.L : 0.f;
         store_row4<T>(dst + 4 * lane, a[0] * inv, a[1] * inv, a[2] * inv, a[3] * inv);
     }
+    if (LSE && lane == 0) *lse_dst = st.L > 0.f ? st.m + logf(st.L) : -INFINITY;
 }
 
 // (Round 5 built a specialised form of the above for the usual case -- one head, head_dim 128, up to eight rows: wave-uniform row
@@ -148,11 +151,11 @@ __device__ inline void merge_finish(const MergeState& st, e16* dst, int lane) {
 
 // One query, NH heads (hq0, hq0 + hq_step, ...; those >= Hq are skipped), start to finish: rows of the query from
 // row_q (list area of `cap` ints in LDS, longer lists in further passes), merge, store.  `have` >= 0:
-// list[0 .. min(have, cap)) already holds the scan.
-template <class T, int D, int CP, int NH>
+// list[0 .. min(have, cap)) already holds the scan.  LSE: lse_q = the query's row of the log-sum-exp output, head stride lse_sh.
+template <class T, int D, int CP, int NH, bool LSE = false>
 __device__ inline void merge_heads_wave(const float* partial_o, const float* partial_lse, const int32_t* row_q, int64_t rows,
                                         int q, int hq0, int hq_step, int Hq, int* list, int cap, int have, e16* out_q,
-                                        int64_t o_sh, int lane) {
+                                        int64_t o_sh, int lane, float* lse_q = nullptr, int64_t lse_sh = 0) {
     __amdgpu_buffer_rsrc_t po[NH], ls[NH];
     MergeState st[NH];
 #pragma unroll
@@ -175,7 +178,9 @@ __device__ inline void merge_heads_wave(const float* partial_o, const float* par
     }
 #pragma unroll
     for (int h = 0; h < NH; ++h)
-        if (hq0 + h * hq_step < Hq) merge_finish<T, D>(st[h], out_q + (int64_t)(hq0 + h * hq_step) * o_sh, lane);
+        if (hq0 + h * hq_step < Hq)
+            merge_finish<T, D, LSE>(st[h], out_q + (int64_t)(hq0 + h * hq_step) * o_sh, lane,
+                                    LSE ? lse_q + (int64_t)(hq0 + h * hq_step) * lse_sh : nullptr);
 }
 
 }  // namespace deft

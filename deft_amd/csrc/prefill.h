@@ -38,6 +38,9 @@ struct PrefillParams {
     int nblk;  // query blocks per sequence in the grid: ceil(max_input_len / 256)
     int Hq, batch;
     unsigned long long* dbg;  // experiments build: per-workgroup wall-clock stamps [workgroup][8], or null
+    // the LSE instantiations (deft_prefill_*_lse): ln sum_j exp(scale q.k_j) of token t and head h at lse[t * lse_st + h * lse_sh]
+    float* lse;
+    int64_t lse_st, lse_sh;  // elements
 };
 
 template <int D>
@@ -49,7 +52,7 @@ struct PrefillSmem {
     static_assert(BYTES <= 160 * 1024, "LDS budget");
 };
 
-template <class T, int D>
+template <class T, int D, bool LSE = false>
 __global__ __launch_bounds__(512, 1) void prefill_kernel(PrefillParams p) {
     using vec8 = typename T::vec8;
     using vec4 = typename T::vec4;
@@ -319,6 +322,10 @@ __global__ __launch_bounds__(512, 1) void prefill_kernel(PrefillParams p) {
                            T::from_float(o[bk][4 * j + 2] * inv), T::from_float(o[bk][4 * j + 3] * inv)};
                 *reinterpret_cast<vec4*>(op + 32 * bk + 8 * j) = v4;
             }
+        // m_run is the maximum of the scores TIMES scale * log2(e) and l_run sums exp2(. - m_run): the natural log-sum-exp of the
+        // scaled scores is (m_run + log2 l_run) ln 2 (both halves of the wave hold the row's values; the lower one stores)
+        if (LSE && h == 0)
+            p.lse[(start + qi) * p.lse_st + (int64_t)head * p.lse_sh] = l_run > 0.f ? (m_run + log2f(l_run)) * LN2 : -INFINITY;
     }
 #ifdef DEFT_EXPERIMENTS
     if (p.dbg && tid == 0 && L < 8192) {
@@ -339,7 +346,7 @@ __global__ __launch_bounds__(512, 1) void prefill_kernel(PrefillParams p) {
 // head_dim 32 and 16 (context_flashattention_nopad.py:134 takes them; no model the reference ships has them): one wave per
 // (query token, query head), the lanes stride over the keys 0 .. i with a private online softmax in fp32 and merge at the end.
 // Correctness path, not a tuned one.  Grid: (ceil(max_input_len / 4) * batch, Hq), 256 threads.
-template <class T, int D>
+template <class T, int D, bool LSE = false>
 __global__ __launch_bounds__(256) void prefill_small_kernel(PrefillParams p) {
     using scalar = typename T::scalar;
     static_assert(D == 32 || D == 16, "small head dimensions");
@@ -389,6 +396,7 @@ __global__ __launch_bounds__(256) void prefill_small_kernel(PrefillParams p) {
         scalar* op = reinterpret_cast<scalar*>(p.o + (start + qi) * p.o_st + (int64_t)head * p.o_sh);
 #pragma unroll
         for (int d = 0; d < D; ++d) op[d] = T::from_float(acc[d] * inv);
+        if (LSE) p.lse[(start + qi) * p.lse_st + (int64_t)head * p.lse_sh] = s > 0.f ? (m + log2f(s)) * LN2 : -INFINITY;  // (m: log2 domain)
     }
 }
 

@@ -112,6 +112,24 @@ def _node_plan(md, NE: int, P: int, total_kv: int, Hq: int, Hkv: int, q_strides,
     return plan
 
 
+def _lse_args(lse, query_states, what: str = "lse"):
+    """The three ABI arguments of a log-sum-exp output (deft_amd/states.py), or none for a plain call; `lse` must be a float32 CUDA
+    tensor [n, heads] -- any strides.  Type and shape here, in front of a call's other checks; the device in _lse_on_device."""
+    if lse is None:
+        return ()
+    if not isinstance(lse, torch.Tensor) or lse.dtype != torch.float32:
+        raise TypeError(f"{what} must be a float32 tensor, got {getattr(lse, 'dtype', type(lse))}")
+    if tuple(lse.shape) != tuple(query_states.shape[:2]):
+        raise ValueError(f"{what} must be [n, heads] = {tuple(query_states.shape[:2])}, got {tuple(lse.shape)}")
+    return (lse.data_ptr(), lse.stride(0), lse.stride(1))
+
+
+def _lse_on_device(lse, what: str = "lse"):
+    """Behind every type and shape check of a call, like the device check of its other tensors."""
+    if lse is not None and not lse.is_cuda:
+        raise DeftLibraryError(f"{what} must be a CUDA (ROCm) tensor; deft_amd has no CPU path")
+
+
 def _i64(t: torch.Tensor, name: str) -> torch.Tensor:
     if t.dtype != torch.int64 or not t.is_cuda:
         raise TypeError(f"{name} must be an int64 CUDA tensor (TreeMetadata contract)")
@@ -132,7 +150,16 @@ def tree_attention_subtree_fwd(
     block_kv: torch.Tensor,  # (kv_len)
     block_lens: torch.Tensor,  # (block_num)
 ) -> None:
+    _flatten_fwd(query_states, key_buffer, value_buffer, output, None, block_len, block_q, block_q_cnts, block_q_offset,
+                 block_bitmasks, block_kv, block_lens)
+
+
+def _flatten_fwd(query_states, key_buffer, value_buffer, output, lse, block_len, block_q, block_q_cnts, block_q_offset,
+                 block_bitmasks, block_kv, block_lens) -> None:
+    """The body of tree_attention_subtree_fwd; with `lse` the *_lse entry point, which also writes every row's log-sum-exp."""
+    lse_args = _lse_args(lse, query_states)  # (first: refused without a GPU as well)
     nq, Hq, Hkv, D = _check_qkv(query_states, key_buffer, value_buffer, output)
+    _lse_on_device(lse)
     if block_len != 128:
         # the reference kernel hard-codes BLOCK_N=128 and ignores this argument (tree_attention.py:655, :922)
         raise ValueError(f"block_len must be 128 (got {block_len})")
@@ -148,11 +175,11 @@ def tree_attention_subtree_fwd(
     scale = 1.0 / (D ** 0.5)  # tree_attention.py:601
     stream = _stream_ptr(query_states)
     plan = _flatten_plan(md, NB, P, Hq, Hkv, (query_states.stride(0), query_states.stride(1)), key_buffer.stride(0), stream)
-    fn, fn_name = entry("deft_flatten_decode", query_states.dtype)
+    fn, fn_name = entry("deft_flatten_decode{}_lse" if lse_args else "deft_flatten_decode", query_states.dtype)
     rc = fn(
         query_states.data_ptr(), query_states.stride(0), query_states.stride(1),
         key_buffer.data_ptr(), value_buffer.data_ptr(), key_buffer.stride(0), key_buffer.stride(1),
-        output.data_ptr(), output.stride(0), output.stride(1),
+        output.data_ptr(), output.stride(0), output.stride(1), *lse_args,
         *[t.data_ptr() for t in md],
         NB, P, nq, Hq, Hkv, D, scale, plan.data_ptr(), ws.data_ptr(), ws_bytes, stream,
     )
@@ -166,8 +193,16 @@ def flatten_append_attention(query_states, kv_layer, output, cache_loc, cache_k,
     (DeFTAttention.deft_flatten_forward, deft_attention.py:110-151): kv_layer[cache_loc, 0/1] = cache_k / cache_v
     and output = Flatten attention that already sees those rows.  kv_layer is one layer of the pool,
     [size, 2, Hkv, D] fp16 or bf16 (memory_pool.py:61-66)."""
+    _flatten_append(query_states, kv_layer, output, None, cache_loc, cache_k, cache_v, block_len, block_q, block_q_cnts,
+                    block_q_offset, block_bitmasks, block_kv, block_lens)
+
+
+def _flatten_append(query_states, kv_layer, output, lse, cache_loc, cache_k, cache_v, block_len, block_q, block_q_cnts,
+                    block_q_offset, block_bitmasks, block_kv, block_lens) -> None:
     key_buffer, value_buffer = kv_layer[:, 0], kv_layer[:, 1]
+    lse_args = _lse_args(lse, query_states)  # (first: refused without a GPU as well)
     nq, Hq, Hkv, D = _check_qkv(query_states, key_buffer, value_buffer, output)
+    _lse_on_device(lse)
     if block_len != 128:
         raise ValueError(f"block_len must be 128 (got {block_len})")
     NB, P = block_q_cnts.shape[0], block_q.shape[0]
@@ -189,11 +224,11 @@ def flatten_append_attention(query_states, kv_layer, output, cache_loc, cache_k,
     stream = _stream_ptr(query_states)
     plan = _flatten_plan(md, NB, P, Hq, Hkv, (query_states.stride(0), query_states.stride(1)), key_buffer.stride(0), stream,
                          cache_loc=cache_loc, new_stride=k.stride(0))
-    fn, fn_name = entry("deft_flatten_decode_append", query_states.dtype)
+    fn, fn_name = entry("deft_flatten_decode_append{}_lse" if lse_args else "deft_flatten_decode_append", query_states.dtype)
     rc = fn(
         query_states.data_ptr(), query_states.stride(0), query_states.stride(1),
         key_buffer.data_ptr(), value_buffer.data_ptr(), key_buffer.stride(0), key_buffer.stride(1),
-        output.data_ptr(), output.stride(0), output.stride(1),
+        output.data_ptr(), output.stride(0), output.stride(1), *lse_args,
         *[t.data_ptr() for t in md],
         NB, P, nq, Hq, Hkv, D, 1.0 / (D ** 0.5),
         cache_loc.data_ptr(), k.data_ptr(), v.data_ptr(), k.stride(0), n,
@@ -215,7 +250,16 @@ def tree_attention_fwd(
     KVMapQ_List_Offset: torch.Tensor,  # (kv_num)
     KVMapQ_List_Len: torch.Tensor,  # (kv_num)
 ) -> None:
+    _node_fwd(query_states, key_buffer, value_buffer, output, None, KV_indices, KV_indices_offset, KV_len, KVMapQ_List,
+              KVMapQ_List_Offset, KVMapQ_List_Len)
+
+
+def _node_fwd(query_states, key_buffer, value_buffer, output, lse, KV_indices, KV_indices_offset, KV_len, KVMapQ_List,
+              KVMapQ_List_Offset, KVMapQ_List_Len) -> None:
+    """The body of tree_attention_fwd; with `lse` the *_lse entry point."""
+    lse_args = _lse_args(lse, query_states)  # (first: refused without a GPU as well)
     nq, Hq, Hkv, D = _check_qkv(query_states, key_buffer, value_buffer, output)
+    _lse_on_device(lse)
     NE = KV_indices_offset.shape[0]
     P = KVMapQ_List.shape[0]
     total_kv = KV_indices.shape[0]
@@ -228,11 +272,11 @@ def tree_attention_fwd(
     stream = _stream_ptr(query_states)
     plan = _node_plan(md, NE, P, total_kv, Hq, Hkv, (query_states.stride(0), query_states.stride(1)),
                       key_buffer.stride(0), stream)
-    fn, fn_name = entry("deft_node_decode", query_states.dtype)
+    fn, fn_name = entry("deft_node_decode{}_lse" if lse_args else "deft_node_decode", query_states.dtype)
     rc = fn(
         query_states.data_ptr(), query_states.stride(0), query_states.stride(1),
         key_buffer.data_ptr(), value_buffer.data_ptr(), key_buffer.stride(0), key_buffer.stride(1),
-        output.data_ptr(), output.stride(0), output.stride(1),
+        output.data_ptr(), output.stride(0), output.stride(1), *lse_args,
         *[t.data_ptr() for t in md],
         NE, P, total_kv, nq, Hq, Hkv, D, scale, plan.data_ptr(), ws.data_ptr(), ws_bytes, stream,
     )
@@ -245,8 +289,16 @@ def node_append_attention(query_states, kv_layer, output, cache_loc, cache_k, ca
     """`store_kv_cache` + `tree_attention_fwd` in ONE launch sequence (DeFTAttention.deft_node_forward,
     deft_attention.py:72-108): kv_layer[cache_loc, 0/1] = cache_k / cache_v and output = Node attention that
     already sees those rows."""
+    _node_append(query_states, kv_layer, output, None, cache_loc, cache_k, cache_v, KV_indices, KV_indices_offset, KV_len,
+                 KVMapQ_List, KVMapQ_List_Offset, KVMapQ_List_Len)
+
+
+def _node_append(query_states, kv_layer, output, lse, cache_loc, cache_k, cache_v, KV_indices, KV_indices_offset, KV_len,
+                 KVMapQ_List, KVMapQ_List_Offset, KVMapQ_List_Len) -> None:
     key_buffer, value_buffer = kv_layer[:, 0], kv_layer[:, 1]
+    lse_args = _lse_args(lse, query_states)  # (first: refused without a GPU as well)
     nq, Hq, Hkv, D = _check_qkv(query_states, key_buffer, value_buffer, output)
+    _lse_on_device(lse)
     NE = KV_indices_offset.shape[0]
     P = KVMapQ_List.shape[0]
     total_kv = KV_indices.shape[0]
@@ -268,11 +320,11 @@ def node_append_attention(query_states, kv_layer, output, cache_loc, cache_k, ca
     stream = _stream_ptr(query_states)
     plan = _node_plan(md, NE, P, total_kv, Hq, Hkv, (query_states.stride(0), query_states.stride(1)),
                       key_buffer.stride(0), stream, cache_loc=cache_loc, new_stride=k.stride(0))
-    fn, fn_name = entry("deft_node_decode_append", query_states.dtype)
+    fn, fn_name = entry("deft_node_decode_append{}_lse" if lse_args else "deft_node_decode_append", query_states.dtype)
     rc = fn(
         query_states.data_ptr(), query_states.stride(0), query_states.stride(1),
         key_buffer.data_ptr(), value_buffer.data_ptr(), key_buffer.stride(0), key_buffer.stride(1),
-        output.data_ptr(), output.stride(0), output.stride(1),
+        output.data_ptr(), output.stride(0), output.stride(1), *lse_args,
         *[t.data_ptr() for t in md],
         NE, P, total_kv, nq, Hq, Hkv, D, 1.0 / (D ** 0.5),
         cache_loc.data_ptr(), k.data_ptr(), v.data_ptr(), k.stride(0), n,

@@ -315,6 +315,158 @@ int deft_prefill_bf16(const void* q, int64_t q_stride_tok, int64_t q_stride_head
                       const int32_t* b_start_loc, const int32_t* b_seq_len, int batch, int max_input_len,
                       int Hq, int Hkv, int D, float scale, void* stream);
 
+/* ---- attention states: an operator's output WITH its log-sum-exp, and the merge of two states --------------------
+ *
+ * The state of query row r and head h over a key set S is the pair (o, lse):
+ *   o[D]  the normalised attention output in the call's element type -- exactly what the plain entry points write;
+ *   lse   = ln sum_{i in S} exp(scale * q.k_i), fp32, natural log, scale included (the convention of the workspace's
+ *         partial log-sum-exps, deft_flatten_read_partials).
+ * The empty set has o = 0 and lse = -inf.  With both halves a caller can join the result with attention over any other set of
+ * keys: another part of the same tree (two calls, two pools, two GPUs), a cached prefix under freshly prefilled tokens, a
+ * sink or window computed elsewhere.
+ *
+ * Names: the element type sits INSIDE these names -- deft_flatten_decode_f16_lse is "the _lse form of deft_flatten_decode_f16",
+ * the merge is deft_merge_f16_states / deft_merge_bf16_states -- so that the names ending in _f16 / _bf16 stay the twelve data
+ * entry points of the plain surface, each with its twin.
+ *
+ * The *_lse entry points below are their plain siblings with one more output: the sibling's exact parameter list with
+ * `lse, lse_stride_tok, lse_stride_head` behind the out strides; lse[q * lse_stride_tok + h * lse_stride_head] (strides in
+ * ELEMENTS, any layout) receives the row's log-sum-exp.  Same kernels, one more 4-byte store per (row, head): `out` is
+ * bit-identical to the plain call's, workspace and plan sizes are the plain call's, a plan built for one serves the other.
+ * lse must be non-null (DEFT_EINVAL: call the plain entry point) and 4-byte aligned.  A query row that no block / entry
+ * lists comes back as (0, -inf).
+ * The rope-fused and the sequential entry points have NO such twin: a caller who needs the log-sum-exp with a rotary
+ * embedding rotates with its own launch (the rope_qk entry point) and calls the *_append_*_lse form.
+ */
+int deft_flatten_decode_f16_lse(
+    const void* q, int64_t q_stride_tok, int64_t q_stride_head,
+    const void* k_base, const void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head,
+    void* out, int64_t o_stride_tok, int64_t o_stride_head,
+    float* lse, int64_t lse_stride_tok, int64_t lse_stride_head,
+    const int64_t* block_q, const int64_t* block_q_cnts, const int64_t* block_q_offset,
+    const int64_t* block_bitmasks, const int64_t* block_kv, const int64_t* block_lens,
+    int NB, int P, int nq, int Hq, int Hkv, int D, float scale,
+    const void* plan, void* workspace, size_t workspace_bytes, void* stream);
+/* bfloat16 twin of deft_flatten_decode_f16_lse: the same contract with bfloat16 elements */
+int deft_flatten_decode_bf16_lse(
+    const void* q, int64_t q_stride_tok, int64_t q_stride_head,
+    const void* k_base, const void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head,
+    void* out, int64_t o_stride_tok, int64_t o_stride_head,
+    float* lse, int64_t lse_stride_tok, int64_t lse_stride_head,
+    const int64_t* block_q, const int64_t* block_q_cnts, const int64_t* block_q_offset,
+    const int64_t* block_bitmasks, const int64_t* block_kv, const int64_t* block_lens,
+    int NB, int P, int nq, int Hq, int Hkv, int D, float scale,
+    const void* plan, void* workspace, size_t workspace_bytes, void* stream);
+int deft_flatten_decode_append_f16_lse(
+    const void* q, int64_t q_stride_tok, int64_t q_stride_head,
+    void* k_base, void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head,
+    void* out, int64_t o_stride_tok, int64_t o_stride_head,
+    float* lse, int64_t lse_stride_tok, int64_t lse_stride_head,
+    const int64_t* block_q, const int64_t* block_q_cnts, const int64_t* block_q_offset,
+    const int64_t* block_bitmasks, const int64_t* block_kv, const int64_t* block_lens,
+    int NB, int P, int nq, int Hq, int Hkv, int D, float scale,
+    const int32_t* cache_loc, const void* k_new, const void* v_new, int64_t new_stride_tok, int n_new,
+    const void* plan, void* workspace, size_t workspace_bytes, void* stream);
+/* bfloat16 twin of deft_flatten_decode_append_f16_lse: the same contract with bfloat16 elements */
+int deft_flatten_decode_append_bf16_lse(
+    const void* q, int64_t q_stride_tok, int64_t q_stride_head,
+    void* k_base, void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head,
+    void* out, int64_t o_stride_tok, int64_t o_stride_head,
+    float* lse, int64_t lse_stride_tok, int64_t lse_stride_head,
+    const int64_t* block_q, const int64_t* block_q_cnts, const int64_t* block_q_offset,
+    const int64_t* block_bitmasks, const int64_t* block_kv, const int64_t* block_lens,
+    int NB, int P, int nq, int Hq, int Hkv, int D, float scale,
+    const int32_t* cache_loc, const void* k_new, const void* v_new, int64_t new_stride_tok, int n_new,
+    const void* plan, void* workspace, size_t workspace_bytes, void* stream);
+int deft_node_decode_f16_lse(
+    const void* q, int64_t q_stride_tok, int64_t q_stride_head,
+    const void* k_base, const void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head,
+    void* out, int64_t o_stride_tok, int64_t o_stride_head,
+    float* lse, int64_t lse_stride_tok, int64_t lse_stride_head,
+    const int64_t* node_kv, const int64_t* node_kv_offset, const int64_t* node_kv_len,
+    const int64_t* node_q, const int64_t* node_q_offset, const int64_t* node_q_len,
+    int NE, int P, int64_t total_kv, int nq, int Hq, int Hkv, int D, float scale,
+    const void* plan, void* workspace, size_t workspace_bytes, void* stream);
+/* bfloat16 twin of deft_node_decode_f16_lse: the same contract with bfloat16 elements */
+int deft_node_decode_bf16_lse(
+    const void* q, int64_t q_stride_tok, int64_t q_stride_head,
+    const void* k_base, const void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head,
+    void* out, int64_t o_stride_tok, int64_t o_stride_head,
+    float* lse, int64_t lse_stride_tok, int64_t lse_stride_head,
+    const int64_t* node_kv, const int64_t* node_kv_offset, const int64_t* node_kv_len,
+    const int64_t* node_q, const int64_t* node_q_offset, const int64_t* node_q_len,
+    int NE, int P, int64_t total_kv, int nq, int Hq, int Hkv, int D, float scale,
+    const void* plan, void* workspace, size_t workspace_bytes, void* stream);
+int deft_node_decode_append_f16_lse(
+    const void* q, int64_t q_stride_tok, int64_t q_stride_head,
+    void* k_base, void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head,
+    void* out, int64_t o_stride_tok, int64_t o_stride_head,
+    float* lse, int64_t lse_stride_tok, int64_t lse_stride_head,
+    const int64_t* node_kv, const int64_t* node_kv_offset, const int64_t* node_kv_len,
+    const int64_t* node_q, const int64_t* node_q_offset, const int64_t* node_q_len,
+    int NE, int P, int64_t total_kv, int nq, int Hq, int Hkv, int D, float scale,
+    const int32_t* cache_loc, const void* k_new, const void* v_new, int64_t new_stride_tok, int n_new,
+    const void* plan, void* workspace, size_t workspace_bytes, void* stream);
+/* bfloat16 twin of deft_node_decode_append_f16_lse: the same contract with bfloat16 elements */
+int deft_node_decode_append_bf16_lse(
+    const void* q, int64_t q_stride_tok, int64_t q_stride_head,
+    void* k_base, void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head,
+    void* out, int64_t o_stride_tok, int64_t o_stride_head,
+    float* lse, int64_t lse_stride_tok, int64_t lse_stride_head,
+    const int64_t* node_kv, const int64_t* node_kv_offset, const int64_t* node_kv_len,
+    const int64_t* node_q, const int64_t* node_q_offset, const int64_t* node_q_len,
+    int NE, int P, int64_t total_kv, int nq, int Hq, int Hkv, int D, float scale,
+    const int32_t* cache_loc, const void* k_new, const void* v_new, int64_t new_stride_tok, int n_new,
+    const void* plan, void* workspace, size_t workspace_bytes, void* stream);
+/* causal prefill with the log-sum-exp of every (token, head) over the tokens 0..i of its sequence: lse[T][Hq] by its strides */
+int deft_prefill_f16_lse(
+    const void* q, int64_t q_stride_tok, int64_t q_stride_head,
+    const void* k, int64_t k_stride_tok, int64_t k_stride_head,
+    const void* v, int64_t v_stride_tok, int64_t v_stride_head,
+    void* out, int64_t o_stride_tok, int64_t o_stride_head,
+    float* lse, int64_t lse_stride_tok, int64_t lse_stride_head,
+    const int32_t* b_start_loc, const int32_t* b_seq_len, int batch, int max_input_len,
+    int Hq, int Hkv, int D, float scale, void* stream);
+/* bfloat16 twin of deft_prefill_f16_lse: the same contract with bfloat16 elements */
+int deft_prefill_bf16_lse(
+    const void* q, int64_t q_stride_tok, int64_t q_stride_head,
+    const void* k, int64_t k_stride_tok, int64_t k_stride_head,
+    const void* v, int64_t v_stride_tok, int64_t v_stride_head,
+    void* out, int64_t o_stride_tok, int64_t o_stride_head,
+    float* lse, int64_t lse_stride_tok, int64_t lse_stride_head,
+    const int32_t* b_start_loc, const int32_t* b_seq_len, int batch, int max_input_len,
+    int Hq, int Hkv, int D, float scale, void* stream);
+/*
+ * (out, lse_out) = merge of the states (o_a, lse_a) and (o_b, lse_b) of n rows x Hq heads over two DISJOINT key sets = the
+ * state over their union, computed in this order:
+ *   m = max(lse_a, lse_b);  if m = -inf the result is (0, -inf);  otherwise
+ *   w_x = exp(lse_x - m),  s = w_a + w_b,  out = (w_a o_a + w_b o_b) / s in fp32, rounded ONCE,  lse_out = m + log s.
+ * A side with lse = -inf has weight exactly 0 and its o is not looked at (it may hold anything, NaN included); merging with
+ * the empty state returns the other state bit for bit.  More than two states: fold pairwise.
+ * o_a, o_b, out: [n][Hq][D] by their strides (elements), head_dim contiguous, D = 16 / 32 / 64 / 128, rows 4-byte aligned
+ * (pointers and strides even) -- 16-byte aligned rows take the 16-byte path, anything else the 4-byte one, chosen per call.
+ * `out` may BE o_a or o_b (the same pointer and strides: every element is read and written by the same lane); any other
+ * overlap of out with an input is the caller's error and is NOT checked.  lse_out may be NULL.
+ * Returns like every other entry point: a status code and the last-error text, no synchronisation, no allocation.
+ */
+int deft_merge_f16_states(
+    const void* o_a, int64_t a_stride_tok, int64_t a_stride_head,
+    const float* lse_a, int64_t lse_a_stride_tok, int64_t lse_a_stride_head,
+    const void* o_b, int64_t b_stride_tok, int64_t b_stride_head,
+    const float* lse_b, int64_t lse_b_stride_tok, int64_t lse_b_stride_head,
+    void* out, int64_t o_stride_tok, int64_t o_stride_head,
+    float* lse_out /* nullable */, int64_t lse_out_stride_tok, int64_t lse_out_stride_head,
+    int n, int Hq, int D, void* stream);
+/* bfloat16 twin of deft_merge_f16_states: the same contract with bfloat16 elements */
+int deft_merge_bf16_states(
+    const void* o_a, int64_t a_stride_tok, int64_t a_stride_head,
+    const float* lse_a, int64_t lse_a_stride_tok, int64_t lse_a_stride_head,
+    const void* o_b, int64_t b_stride_tok, int64_t b_stride_head,
+    const float* lse_b, int64_t lse_b_stride_tok, int64_t lse_b_stride_head,
+    void* out, int64_t o_stride_tok, int64_t o_stride_head,
+    float* lse_out /* nullable */, int64_t lse_out_stride_tok, int64_t lse_out_stride_head,
+    int n, int Hq, int D, void* stream);
+
 /* ---- rotary position embedding of this step's q / k rows (the op in front of the path) -----------------
  *
  * In place, like RotaryEmbedding.forward_cuda (DeFT/deft/layers/rotary_embedding.py:157-177 ->
