@@ -20,11 +20,20 @@ from .states import (  # noqa: F401
     merge_attention_states,
     node_append_attention_lse,
     prefill_with_cached_prefix,
+    tree_attention_fwd_kv8_lse,
     tree_attention_fwd_lse,
+    tree_attention_subtree_fwd_kv8_lse,
     tree_attention_subtree_fwd_lse,
 )
 from .token_attention import token_attention_fwd  # noqa: F401
-from .tree_attention import kv_append, tree_attention_fwd, tree_attention_subtree_fwd  # noqa: F401
+from .tree_attention import (  # noqa: F401
+    kv_append,
+    kv_append_kv8,
+    tree_attention_fwd,
+    tree_attention_fwd_kv8,
+    tree_attention_subtree_fwd,
+    tree_attention_subtree_fwd_kv8,
+)
 from .tree_cache import (  # noqa: F401
     BLOCK_CONFIG,
     ExtendStep,

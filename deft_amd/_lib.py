@@ -143,6 +143,25 @@ for _s in ("_f16", "_bf16"):
     getattr(lib, "deft_merge" + _s + "_states").argtypes = [_vp, _i64, _i64] * 6 + [_i32, _i32, _i32, _vp]
     getattr(lib, "deft_merge" + _s + "_states").restype = C.c_int
 
+# fp8 KV pools (OCP e4m3fn codes with per-KV-head fp32 scales; deft_amd/tree_attention.py *_kv8): the plain sibling's arguments with
+# `k_scale, v_scale` (device pointers, None = ones) directly behind kv_stride_head.  The element type of q / out / the new rows sits
+# INSIDE the name here too.
+KV8_ENTRY_POINTS = ("deft_flatten_decode{}_kv8", "deft_flatten_decode{}_kv8_lse", "deft_node_decode{}_kv8", "deft_node_decode{}_kv8_lse",
+                    "deft_kv_append{}_kv8")
+KV8_DTYPE = torch.float8_e4m3fn
+_SCALES = [_vp, _vp]
+for _f, _at in (("deft_flatten_decode", len(_QKV)), ("deft_node_decode", len(_QKV)), ("deft_kv_append", 4)):
+    _plain = list(getattr(lib, _f + "_f16").argtypes)
+    for _s in ("_f16", "_bf16"):
+        if not hasattr(lib, _f + _s + "_kv8"):  # (DEFT_AMD_LIB may name an older build: `entry` says so)
+            continue
+        _kv8 = _plain[:_at] + _SCALES + _plain[_at:]
+        getattr(lib, _f + _s + "_kv8").argtypes = _kv8
+        getattr(lib, _f + _s + "_kv8").restype = C.c_int
+        if _f != "deft_kv_append":
+            getattr(lib, _f + _s + "_kv8_lse").argtypes = _with_lse(_kv8, len(_QKV + _SCALES + _OUT))
+            getattr(lib, _f + _s + "_kv8_lse").restype = C.c_int
+
 _SUFFIX = {torch.float16: "_f16", torch.bfloat16: "_bf16"}
 ELEM_DTYPES = tuple(_SUFFIX)
 
@@ -172,7 +191,8 @@ def entry(name: str, dtype):
     the suffix goes (STATE_ENTRY_POINTS)."""
     full = name.format(elem_suffix(dtype)) if "{}" in name else name + elem_suffix(dtype)
     if not hasattr(lib, full):
-        raise DeftLibraryError(f"{LIB_PATH} does not export {full}: a build from before the bfloat16 entry points")
+        raise DeftLibraryError(f"{LIB_PATH} does not export {full}: a build from before " +
+                               ("the fp8 KV pool entry points" if "_kv8" in full else "the bfloat16 entry points"))
     return getattr(lib, full), full
 
 
@@ -248,7 +268,7 @@ EXPORTED = (
     "deft_prefill_f16", "deft_rope_qk_f16", "deft_seq_plan_bytes", "deft_seq_workspace_bytes", "deft_seq_build_plan", "deft_seq_decode_f16", "deft_seq_decode_append_f16",
     "deft_kv_append_f16", "deft_probe_stream_read", "deft_md_build", "deft_md_sizes", "deft_md_fetch", "deft_md_free",
     "deft_tree_create",
-) + tuple(_f + "_bf16" for _f in ELEM_ENTRY_POINTS) + tuple(_f.format(_s) for _f in STATE_ENTRY_POINTS for _s in ("_f16", "_bf16")) + tuple(_TREE_FUNCS)
+) + tuple(_f + "_bf16" for _f in ELEM_ENTRY_POINTS) + tuple(_f.format(_s) for _f in STATE_ENTRY_POINTS + KV8_ENTRY_POINTS for _s in ("_f16", "_bf16")) + tuple(_TREE_FUNCS)
 
 _ERR_NAMES = {-1: "DEFT_EINVAL", -2: "DEFT_EUNSUPPORTED", -3: "DEFT_EHIP", -4: "DEFT_EWORKSPACE"}
 

@@ -82,6 +82,38 @@ static Tensors plan_geometry(int Hq, int Hkv, int64_t q_st, int64_t q_sh, int64_
     return t;
 }
 
+// An fp8 (OCP e4m3fn) K/V pool, the *_kv8 entry points: the per-KV-head scales (device pointers, null = ones) and the checks that
+// differ from a 16-bit pool's -- Tensors::check() still runs behind them.  Pool strides are in bytes there.
+struct Kv8 {
+    const float* k_scale;
+    const float* v_scale;
+
+    int check(const Tensors& t) const {
+        if (t.D != 128) {
+            set_error("fp8 KV pool: head_dim %d is not supported (head_dim must be 128; 64, 32 and 16 are not built for fp8 pools)", t.D);
+            return DEFT_EUNSUPPORTED;
+        }
+        if (t.kv_ss % 2) {
+            set_error("fp8 KV pool: odd slot stride %lld (the plan addresses rows in 2-byte units)", (long long)t.kv_ss);
+            return DEFT_EINVAL;
+        }
+        if (!aligned16(t.k) || !aligned16(t.v) || (t.kv_ss % 16) || (t.kv_sh % 16)) {
+            set_error("fp8 KV pool: base pointers and the slot stride must be 16-byte aligned, the head stride a multiple of 16");
+            return DEFT_EINVAL;
+        }
+        if ((reinterpret_cast<uintptr_t>(k_scale) | reinterpret_cast<uintptr_t>(v_scale)) & 3u) {
+            set_error("fp8 KV pool: k_scale / v_scale must be 4-byte aligned");
+            return DEFT_EINVAL;
+        }
+        return DEFT_OK;
+    }
+    // what the plan builders and Tensors::check() see: the slot stride in 2-byte units (a record's byte offset is slot * stride * 2)
+    static Tensors as_plan_tensors(Tensors t) {
+        t.kv_ss /= 2;
+        return t;
+    }
+};
+
 // DeFT-Flatten metadata: the six block arrays, NB blocks, P (query, block) pairs = partial rows per head.
 struct FlattenMd {
     const int64_t *block_q, *block_q_cnts, *block_q_offset, *block_bitmasks, *block_kv, *block_lens;

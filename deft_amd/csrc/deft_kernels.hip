@@ -335,6 +335,7 @@ __global__ __launch_bounds__(256, 2) void stage1_kernel(Stage1Params p) {
 #include "window.h"
 #include "merge.h"
 #include "stage1_np.h"
+#include "stage1_kv8.h"
 #include "prefill.h"
 namespace deft {
 
@@ -616,7 +617,8 @@ static int num_cus() {
     return d.cus;
 }
 enum : unsigned { ATTR_NP = 4,  // (bits 0-1, 8-11: the head_dim 64 / 32 / 16 kernels)
-                  ATTR_UNITS = 8, ATTR_NODE_UNITS = 16, ATTR_PREFILL = 32, ATTR_TREE = 64, ATTR_NP_ROPE = 128, ATTR_NP_T = 8192, ATTR_NP_ROPE_T = 16384, ATTR_NP_HD2 = 32768, ATTR_NP_HD2_T = 65536, ATTR_PREFILL_64 = 1u << 17, ATTR_NP_DYN = 1u << 18, ATTR_NP_ROPE_DYN = 1u << 19, ATTR_NP_HD2_DYN = 1u << 20, ATTR_PREFILL_LSE = 1u << 21, ATTR_PREFILL_64_LSE = 1u << 22 };
+                  ATTR_UNITS = 8, ATTR_NODE_UNITS = 16, ATTR_PREFILL = 32, ATTR_TREE = 64, ATTR_NP_ROPE = 128, ATTR_NP_T = 8192, ATTR_NP_ROPE_T = 16384, ATTR_NP_HD2 = 32768, ATTR_NP_HD2_T = 65536, ATTR_PREFILL_64 = 1u << 17, ATTR_NP_DYN = 1u << 18, ATTR_NP_ROPE_DYN = 1u << 19, ATTR_NP_HD2_DYN = 1u << 20, ATTR_PREFILL_LSE = 1u << 21, ATTR_PREFILL_64_LSE = 1u << 22,
+                  ATTR_KV8 = 1u << 23, ATTR_KV8_T = 1u << 24, ATTR_KV8_DYN = 1u << 25 };
 template <class T>
 constexpr uint64_t attr_bit(unsigned bit) { return std::is_same<T, BF16>::value ? (uint64_t)bit << 32 : (uint64_t)bit; }
 static int raise_lds(const void* fn, int bytes, uint64_t bit, const char* what) {  // idempotent; races are harmless
@@ -1308,6 +1310,134 @@ static int kv_append_impl(void* k_base, void* v_base, int64_t kv_stride_slot, in
     return check_launch("kv_append launch");
 }
 
+// ---------------------------------------------------------------------------
+// fp8 KV pools (stage1_kv8.h): the *_kv8 entry points.  Plan builders, workspace, merge are the 16-bit path's own; only stage 1
+// and the append differ.  There is no fused append: the plans are built with cache_loc = NULL.
+// ---------------------------------------------------------------------------
+template <class T>
+static int launch_stage1_kv8(const Stage1Params& p, int64_t unit_cap, const PlanView& pv, const Kv8& s8, hipStream_t stream, int nq) {
+    using SM = Kv8Smem;
+    // the launch rules of launch_stage1_np (cache policy, DYN, grid cap, mirrored order), which depend on the plan and the geometry alone
+    const bool nt = p.G > 1 || (int64_t)nq <= 1024;
+    const bool small_gqa = unit_cap * p.Hkv <= 16LL * num_cus();
+    const bool dyn = nt && p.G > 1 && (small_gqa || (int64_t)nq * p.G > 160);
+    void (*kernel)(Kv8Params) = dyn ? &stage1_kv8_kernel<T, true, true> : nt ? &stage1_kv8_kernel<T, true> : &stage1_kv8_kernel<T, false>;
+    const int rc = raise_lds(reinterpret_cast<const void*>(kernel), SM::BYTES, attr_bit<T>(dyn ? ATTR_KV8_DYN : nt ? ATTR_KV8 : ATTR_KV8_T),
+                             "stage1_kv8");
+    if (rc) return rc;
+    if (unit_cap <= 0) return DEFT_OK;
+    int64_t grid = unit_cap * p.Hkv;
+    if (grid > 0x7fffffffLL) {
+        set_error("stage1 grid too large: %lld", (long long)grid);
+        return DEFT_EINVAL;
+    }
+    const int capx = p.G > 1 ? 1 : 3;
+    const int64_t cap_wgs = (int64_t)capx * 2LL * num_cus();
+    if (grid > cap_wgs) grid = cap_wgs;
+    const int gx = knob("DEFT_NP_GRID", 0);  // (experiments build, tests: a tiny grid = many rounds of the item loop)
+    if (gx > 0 && grid > gx) grid = gx;
+    Kv8Params kp{};
+    kp.s = p;
+    kp.plan = pv.records;
+    kp.hdr = pv.hdr;
+    kp.mirror = knob("DEFT_NP_MIRROR", dyn && small_gqa ? 1 : 0) != 0 && dyn ? 1 : 0;
+    kp.fast_n = 2 * num_cus();
+    kp.k_scale = s8.k_scale;
+    kp.v_scale = s8.v_scale;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(256), SM::BYTES, stream, kp);
+    return check_launch("stage1 kv8 launch");
+}
+
+template <class T>
+static int flatten_decode_kv8_impl(const Tensors& t, const Kv8& s8, const FlattenMd& md, const Scratch& sc) {
+    int rc = s8.check(t);
+    if (rc) return rc;
+    rc = t.check();
+    if (rc) return rc;
+    rc = sc.check();
+    if (rc) return rc;
+    rc = md.check();
+    if (rc) return rc;
+    const int64_t cap = md.cap(t.G());
+    const Workspace ws = carve(sc.workspace, t.Hq, t.D, md.P, 0, plan_view(nullptr, cap, md.P).bytes);
+    rc = sc.holds(ws);
+    if (rc) return rc;
+    Stage1Params p{};
+    Kv8::as_plan_tensors(t).fill(p);  // (kv_ss in 2-byte units: what the plan kernels multiply a slot by)
+    md.fill(p);
+    p.partial_o = ws.partial_o;
+    p.partial_lse = ws.partial_lse;
+    p.row_q = ws.row_q;
+    PlanView pv;
+    if (sc.plan) {
+        pv = plan_view(const_cast<void*>(sc.plan), cap, md.P);
+    } else {
+        pv = plan_view(ws.plan, cap, md.P);
+        rc = launch_plan(p, md.NB, pv, AppendArgs(), sc.st());
+        if (rc) return rc;
+    }
+    rc = launch_stage1_kv8<T>(p, cap, pv, s8, sc.st(), t.nq);
+    if (rc) return rc;
+    return launch_merge<T>(t.D, ws, &pv, pv.row_q, md.P, t.out, t.o_st, t.o_sh, t.nq, t.Hq, t.G(), sc.st(), t.lse, t.lse_st, t.lse_sh);
+}
+
+template <class T>
+static int node_decode_kv8_impl(const Tensors& t, const Kv8& s8, const NodeMd& md, const Scratch& sc) {
+    int rc = s8.check(t);
+    if (rc) return rc;
+    rc = t.check();
+    if (rc) return rc;
+    rc = md.check();
+    if (rc) return rc;
+    rc = sc.check();
+    if (rc) return rc;
+    const int G = t.G();
+    const int64_t tiles = md.tiles(), rows = md.rows();
+    const Workspace ws = carve(sc.workspace, t.Hq, t.D, rows, tiles, md.plan(nullptr, G).bytes);
+    rc = sc.holds(ws);
+    if (rc) return rc;
+    Stage1Params p{};
+    Kv8::as_plan_tensors(t).fill(p);
+    md.fill(p);
+    p.partial_o = ws.partial_o;
+    p.partial_lse = ws.partial_lse;
+    p.row_q = ws.row_q;
+    PlanView pv;
+    if (sc.plan) {
+        pv = md.plan(const_cast<void*>(sc.plan), G);
+    } else {
+        pv = md.plan(ws.plan, G);
+        rc = launch_node_plan(p, md.NE, rows, pv, AppendArgs(), sc.st());
+        if (rc) return rc;
+    }
+    rc = launch_stage1_kv8<T>(p, tiles * G, pv, s8, sc.st(), t.nq);
+    if (rc) return rc;
+    return launch_merge<T>(t.D, ws, &pv, pv.row_q, rows, t.out, t.o_st, t.o_sh, t.nq, t.Hq, G, sc.st(), t.lse, t.lse_st, t.lse_sh);
+}
+
+template <class T>
+static int kv8_append_impl(void* k_base, void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head, const float* k_scale,
+                           const float* v_scale, const int32_t* cache_loc, const void* k_new, const void* v_new,
+                           int64_t new_stride_tok, int n, int Hkv, int D, void* stream) {
+    if (n == 0) return DEFT_OK;
+    if (!k_base || !v_base || !cache_loc || !k_new || !v_new || n < 0 || Hkv <= 0 || D <= 0 || (D % 8)) {
+        set_error("bad kv_append arguments (n=%d Hkv=%d D=%d)", n, Hkv, D);
+        return DEFT_EINVAL;
+    }
+    if (!aligned16(k_new) || !aligned16(v_new) || (new_stride_tok % 8) || ((reinterpret_cast<uintptr_t>(k_base) | reinterpret_cast<uintptr_t>(v_base)) & 7u) ||
+        (kv_stride_slot % 8) || (kv_stride_head % 8) || ((reinterpret_cast<uintptr_t>(k_scale) | reinterpret_cast<uintptr_t>(v_scale)) & 3u)) {
+        set_error("kv_append (fp8 pool): new rows must be 16-byte aligned, pool rows 8-byte aligned");
+        return DEFT_EINVAL;
+    }
+    const int64_t total = (int64_t)n * Hkv * (D / 8);
+    const int64_t blocks = (total + 255) / 256;
+    const unsigned grid = (unsigned)(blocks < 2048 ? blocks : 2048);
+    hipLaunchKernelGGL(kv8_append_kernel<T>, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), static_cast<uint8_t*>(k_base),
+                       static_cast<uint8_t*>(v_base), kv_stride_slot, kv_stride_head, cache_loc, static_cast<const e16*>(k_new),
+                       static_cast<const e16*>(v_new), new_stride_tok, n, Hkv, D, k_scale, v_scale);
+    return check_launch("kv_append (fp8 pool) launch");
+}
+
 extern "C" int deft_flatten_read_partials(const void* workspace, size_t workspace_bytes, int NB, int P, int nq, int Hq, int Hkv, int D,
                                float* partial_o_dev, float* partial_lse_dev, void* stream) {
     (void)nq;
@@ -1772,6 +1902,40 @@ DEFT_STATE_TWINS(node_decode_append, _lse, (const void* q, int64_t q_stride_tok,
     if (int rc = make_append(ap, APPEND)) return rc;
     return node_decode_impl<T>(TENSORS_LSE, NODE_MD, ap, SCRATCH);
 })
+#define KV8 Kv8{k_scale, v_scale}
+DEFT_STATE_TWINS(flatten_decode, _kv8, (const void* q, int64_t q_stride_tok, int64_t q_stride_head, const void* k_base, const void*
+            v_base, int64_t kv_stride_slot, int64_t kv_stride_head, const float* k_scale, const float* v_scale, void* out,
+            int64_t o_stride_tok, int64_t o_stride_head, const int64_t* block_q, const int64_t* block_q_cnts, const int64_t*
+            block_q_offset, const int64_t* block_bitmasks, const int64_t* block_kv, const int64_t* block_lens, int NB, int P, int
+            nq, int Hq, int Hkv, int D, float scale, const void* plan, void* workspace, size_t workspace_bytes, void* stream),
+           { return flatten_decode_kv8_impl<T>(TENSORS, KV8, FLATTEN_MD, SCRATCH); })
+DEFT_STATE_TWINS(flatten_decode, _kv8_lse, (const void* q, int64_t q_stride_tok, int64_t q_stride_head, const void* k_base, const void*
+            v_base, int64_t kv_stride_slot, int64_t kv_stride_head, const float* k_scale, const float* v_scale, void* out,
+            int64_t o_stride_tok, int64_t o_stride_head, float* lse, int64_t lse_stride_tok, int64_t lse_stride_head, const
+            int64_t* block_q, const int64_t* block_q_cnts, const int64_t* block_q_offset, const int64_t* block_bitmasks, const
+            int64_t* block_kv, const int64_t* block_lens, int NB, int P, int nq, int Hq, int Hkv, int D, float scale, const void*
+            plan, void* workspace, size_t workspace_bytes, void* stream),
+           { return flatten_decode_kv8_impl<T>(TENSORS_LSE, KV8, FLATTEN_MD, SCRATCH); })
+DEFT_STATE_TWINS(node_decode, _kv8, (const void* q, int64_t q_stride_tok, int64_t q_stride_head, const void* k_base, const void* v_base,
+            int64_t kv_stride_slot, int64_t kv_stride_head, const float* k_scale, const float* v_scale, void* out, int64_t
+            o_stride_tok, int64_t o_stride_head, const int64_t* node_kv, const int64_t* node_kv_offset, const int64_t*
+            node_kv_len, const int64_t* node_q, const int64_t* node_q_offset, const int64_t* node_q_len, int NE, int P, int64_t
+            total_kv, int nq, int Hq, int Hkv, int D, float scale, const void* plan, void* workspace, size_t workspace_bytes,
+            void* stream),
+           { return node_decode_kv8_impl<T>(TENSORS, KV8, NODE_MD, SCRATCH); })
+DEFT_STATE_TWINS(node_decode, _kv8_lse, (const void* q, int64_t q_stride_tok, int64_t q_stride_head, const void* k_base, const void* v_base,
+            int64_t kv_stride_slot, int64_t kv_stride_head, const float* k_scale, const float* v_scale, void* out, int64_t
+            o_stride_tok, int64_t o_stride_head, float* lse, int64_t lse_stride_tok, int64_t lse_stride_head, const int64_t*
+            node_kv, const int64_t* node_kv_offset, const int64_t* node_kv_len, const int64_t* node_q, const int64_t*
+            node_q_offset, const int64_t* node_q_len, int NE, int P, int64_t total_kv, int nq, int Hq, int Hkv, int D, float
+            scale, const void* plan, void* workspace, size_t workspace_bytes, void* stream),
+           { return node_decode_kv8_impl<T>(TENSORS_LSE, KV8, NODE_MD, SCRATCH); })
+DEFT_STATE_TWINS(kv_append, _kv8, (void* k_base, void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head, const float* k_scale,
+            const float* v_scale, const int32_t* cache_loc, const void* k_new, const void* v_new, int64_t new_stride_tok, int n,
+            int Hkv, int D, void* stream),
+           { return kv8_append_impl<T>(k_base, v_base, kv_stride_slot, kv_stride_head, k_scale, v_scale, cache_loc, k_new, v_new,
+                                       new_stride_tok, n, Hkv, D, stream); })
+#undef KV8
 #undef TENSORS_LSE
 DEFT_STATE_TWINS(prefill, _lse, (const void* q, int64_t q_stride_tok, int64_t q_stride_head, const void* k, int64_t k_stride_tok, int64_t
             k_stride_head, const void* v, int64_t v_stride_tok, int64_t v_stride_head, void* out, int64_t o_stride_tok,

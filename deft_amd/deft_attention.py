@@ -23,8 +23,8 @@ from ._lib import DeftLibraryError, check, entry, lib, same_elem_dtype, tensor_v
 from .forward_mode import ForwardMode, InputMetadata
 from .context_attention import context_attention_fwd
 from .token_attention import seq_append_attention, token_attention_fwd
-from .tree_attention import (flatten_append_attention, node_append_attention, tree_attention_fwd,
-                             tree_attention_subtree_fwd)
+from .tree_attention import (flatten_append_attention, node_append_attention, tree_attention_fwd, tree_attention_fwd_kv8,
+                             tree_attention_subtree_fwd, tree_attention_subtree_fwd_kv8)
 from .tree_cache import get_global_tree_metadata
 
 
@@ -372,6 +372,8 @@ class DeFTAttention(nn.Module):
         fused vs rope + attention, ToT-50 27.2 vs 26.0, the north-star tree 43.7 vs 42.6: on the HBM-bound trees the
         cos|sin fetch and the LDS pass in front of every workgroup's first MFMA cost more than the 3 us launch they save)."""
         mode = input_metadata.forward_mode
+        if getattr(input_metadata.token_to_kv_pool, "is_fp8", False):
+            return self.kv8_forward(q, k, v, input_metadata, rotary_emb, positions, fuse_rope)
         if rotary_emb is not None:
             if positions is None:
                 raise ValueError("rotary_emb needs positions")
@@ -409,6 +411,49 @@ class DeFTAttention(nn.Module):
         raise NotImplementedError(
             f"Unsupported forward mode: {mode} (deft_amd covers TREE_DECODE_FLATTEN, TREE_DECODE_NODE, EXTEND, DECODE and PREFILL with paged KV)"
         )
+
+    def kv8_forward(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, input_metadata: InputMetadata,
+                    rotary_emb=None, positions: torch.Tensor = None, fuse_rope: bool = None) -> torch.Tensor:
+        """`forward` over an fp8 KV pool (TokenToKVPool(dtype=torch.float8_e4m3fn)): the two tree decode modes (node_chunk included:
+        it is Node metadata) and PREFILL.  Two launches per layer -- the quantising append (store_kv_cache), then the kv8 operator with
+        the layer's per-head scales; a given rotary embedding runs first with its own launch.  There is no fused append, no fused
+        rotary embedding, no extend step and no sequential comparator for fp8 pools: those are refused, never misread as 16-bit."""
+        mode = input_metadata.forward_mode
+        pool = input_metadata.token_to_kv_pool
+        if fuse_rope:
+            raise NotImplementedError("fuse_rope=True: the rope-fused entry points do not take an fp8 KV pool (pass fuse_rope=None or False)")
+        if mode == ForwardMode.EXTEND:
+            raise NotImplementedError("ForwardMode.EXTEND over an fp8 KV pool is not implemented")
+        if mode == ForwardMode.DECODE:
+            raise NotImplementedError("ForwardMode.DECODE (the sequential comparator) over an fp8 KV pool is not implemented")
+        if mode not in (ForwardMode.PREFILL, ForwardMode.TREE_DECODE_FLATTEN, ForwardMode.TREE_DECODE_NODE):
+            raise NotImplementedError(f"Unsupported forward mode over an fp8 KV pool: {mode}")
+        if rotary_emb is not None:
+            if positions is None:
+                raise ValueError("rotary_emb needs positions")
+            rotated = rotary_emb(positions, q, k)
+            if rotated is not None:
+                q, k = rotated
+        if mode == ForwardMode.PREFILL:
+            return self.prefill_forward_triton(q, k, v, input_metadata)  # (store_kv_cache quantises the prompt's rows)
+        md = get_global_tree_metadata()
+        assert md is not None and pool is not None
+        if getattr(md, "extend_step", None) is not None:
+            raise NotImplementedError("the registered TreeMetadata is an extend step's: not implemented over an fp8 KV pool")
+        _check_query_tile(md)
+        Hq, Hkv, D = self.tp_q_head_num, self.tp_k_head_num, self.head_dim
+        o = torch.empty((q.shape[0], Hq * D), dtype=q.dtype, device=q.device)
+        self.store_kv_cache(k.view(-1, Hkv, D), v.view(-1, Hkv, D), input_metadata)
+        q3, o3 = q.view(-1, Hq, D), o.view(-1, Hq, D)
+        kb, vb = pool.get_key_buffer(self.layer_id), pool.get_value_buffer(self.layer_id)
+        ks, vs = pool.k_scale[self.layer_id], pool.v_scale[self.layer_id]
+        if mode == ForwardMode.TREE_DECODE_FLATTEN:
+            tree_attention_subtree_fwd_kv8(q3, kb, vb, o3, md.block_len, md.block_q, md.block_q_cnts, md.block_q_offset,
+                                           md.block_bitmasks, md.block_kv, md.block_lens, k_scale=ks, v_scale=vs)
+        else:
+            tree_attention_fwd_kv8(q3, kb, vb, o3, md.node_kv, md.node_kv_offset, md.node_kv_len, md.node_q, md.node_q_offset,
+                                   md.node_q_len, k_scale=ks, v_scale=vs)
+        return o
 
     def store_kv_cache(self, cache_k: torch.Tensor, cache_v: torch.Tensor, input_metadata: InputMetadata) -> None:
         input_metadata.kv_updater.update(self.layer_id, cache_k, cache_v)

@@ -73,6 +73,8 @@ class Forest:
     def __init__(self, trees: Sequence[TreeCache]) -> None:
         assert len(trees) > 0
         pool = trees[0].token_to_kv_pool
+        if getattr(pool, "is_fp8", False):
+            raise NotImplementedError("Forest over an fp8 KV pool is not implemented (fp8 pools serve single-tree decode steps)")
         for t in trees:
             assert t.token_to_kv_pool is pool, "all trees of a forest live in one KV pool"
             assert t.root is not None

@@ -2,7 +2,7 @@
 
 Mirrors DeFT/deft/memory_pool.py:
   ReqToTokenPool (:11-45)   leaf -> slot page table [requests, ctx] int32
-  TokenToKVPool  (:48-108)  per layer kv_data[layer] = [size, 2, Hkv, D] fp16;
+  TokenToKVPool  (:48-108)  per layer kv_data[layer] = [size, 2, Hkv, D] fp16 / bf16, or float8_e4m3fn with per-head scales;
                             K view = [:, 0], V view = [:, 1]; int16 refcount per
                             slot; alloc = the lowest free slots (:74-80)
 
@@ -76,6 +76,23 @@ class TokenToKVPool:
         self._storage = torch.empty((layer_num, size, 2, head_num, head_dim), dtype=dtype, device=device)
         self.device = self._storage.device  # (WITH its index: torch.device("cuda") != torch.device("cuda:0"))
         self.kv_data = [self._storage[i] for i in range(layer_num)]
+        # An fp8 pool (dtype=torch.float8_e4m3fn: OCP e4m3fn codes, half the bytes and twice the slots of a 16-bit pool) carries
+        # per-layer, per-KV-head fp32 scales on the pool's device -- a stored code c of head h means float(c) * scale[h] -- ones
+        # until set_kv_scales; a 16-bit pool has none.
+        self.is_fp8 = dtype == torch.float8_e4m3fn
+        self.k_scale = torch.ones((layer_num, head_num), dtype=torch.float32, device=device) if self.is_fp8 else None
+        self.v_scale = torch.ones((layer_num, head_num), dtype=torch.float32, device=device) if self.is_fp8 else None
+
+    def set_kv_scales(self, layer_id: int, k_scale, v_scale) -> None:
+        """The per-KV-head scales of one layer of an fp8 pool (finite and > 0: the caller's promise, nothing reads them back).
+        Codes already stored keep their bytes: set the scales before the layer's first append."""
+        if not self.is_fp8:
+            raise TypeError(f"set_kv_scales: the pool is {self._storage.dtype}, only a float8_e4m3fn pool has scales")
+        for dst, src, name in ((self.k_scale, k_scale, "k_scale"), (self.v_scale, v_scale, "v_scale")):
+            src = torch.as_tensor(src, dtype=torch.float32).reshape(-1)
+            if src.numel() != self.head_num:
+                raise ValueError(f"{name} must hold one scale per KV head ({self.head_num}), got {src.numel()}")
+            dst[layer_id].copy_(src)
 
     def get_key_buffer(self, layer_id: int) -> torch.Tensor:
         return self.kv_data[layer_id][:, 0]

@@ -111,6 +111,9 @@ class DecodeSession:
         `incremental`: window plans (module docstring).  `win_tiles`: overflow tiles per query chunk (None: enough for ~16 steps of
         nq tokens, between 2 and 8)."""
         pool = tree.token_to_kv_pool
+        if getattr(pool, "is_fp8", False):
+            raise NotImplementedError("DecodeSession over an fp8 KV pool is not implemented (no captured steps or window plans for fp8 "
+                                      "pools; run the steps through DeFTAttention.forward)")
         assert pool.device.type == "cuda" and mode in ("flatten", "node")
         assert head_dim == 128 or (head_dim == 64 and num_kv_heads % 2 == 0), "DecodeSession: head_dim 128, or 64 with an even number of KV heads"
         assert capture_after == "auto" or int(capture_after) >= 1

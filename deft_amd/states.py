@@ -19,10 +19,12 @@ import torch
 
 from ._lib import DeftLibraryError, check, entry, same_elem_dtype
 from .context_attention import _prefill
-from .tree_attention import _flatten_append, _flatten_fwd, _lse_args, _node_append, _node_fwd, _stream_ptr, kv_append
+from .tree_attention import (_flatten_append, _flatten_fwd, _flatten_fwd_kv8, _lse_args, _node_append, _node_fwd, _node_fwd_kv8,
+                             _stream_ptr, kv_append)
 
 __all__ = ["tree_attention_subtree_fwd_lse", "tree_attention_fwd_lse", "flatten_append_attention_lse", "node_append_attention_lse",
-           "context_attention_fwd_lse", "merge_attention_states", "cached_prefix_blocks", "prefill_with_cached_prefix"]
+           "context_attention_fwd_lse", "merge_attention_states", "cached_prefix_blocks", "prefill_with_cached_prefix",
+           "tree_attention_subtree_fwd_kv8_lse", "tree_attention_fwd_kv8_lse"]
 
 
 def _need(lse):
@@ -45,6 +47,23 @@ def tree_attention_fwd_lse(query_states, key_buffer, value_buffer, output, lse, 
     """`tree_attention_fwd` (DeFT-Node) that also writes lse[q, h]."""
     _node_fwd(query_states, key_buffer, value_buffer, output, _need(lse), KV_indices, KV_indices_offset, KV_len, KVMapQ_List,
               KVMapQ_List_Offset, KVMapQ_List_Len)
+
+
+@torch.inference_mode()
+def tree_attention_subtree_fwd_kv8_lse(query_states, key_buffer, value_buffer, output, lse, block_len, block_q, block_q_cnts,
+                                       block_q_offset, block_bitmasks, block_kv, block_lens, k_scale=None, v_scale=None, scale=None) -> None:
+    """`tree_attention_subtree_fwd_kv8` (DeFT-Flatten over an fp8 pool) that also writes lse[q, h]: the state combines with any
+    other through `merge_attention_states`."""
+    _flatten_fwd_kv8(query_states, key_buffer, value_buffer, output, _need(lse), block_len, block_q, block_q_cnts, block_q_offset,
+                     block_bitmasks, block_kv, block_lens, k_scale, v_scale, scale)
+
+
+@torch.inference_mode()
+def tree_attention_fwd_kv8_lse(query_states, key_buffer, value_buffer, output, lse, KV_indices, KV_indices_offset, KV_len, KVMapQ_List,
+                               KVMapQ_List_Offset, KVMapQ_List_Len, k_scale=None, v_scale=None, scale=None) -> None:
+    """`tree_attention_fwd_kv8` (DeFT-Node over an fp8 pool) that also writes lse[q, h]."""
+    _node_fwd_kv8(query_states, key_buffer, value_buffer, output, _need(lse), KV_indices, KV_indices_offset, KV_len, KVMapQ_List,
+                  KVMapQ_List_Offset, KVMapQ_List_Len, k_scale, v_scale, scale)
 
 
 @torch.inference_mode()
@@ -156,6 +175,8 @@ def prefill_with_cached_prefix(q, k, v, out, kv_layer, path_slots, new_slots, ls
     at every call.  The one measurement there is (profiles/states_cost.txt: 4096 cached tokens, Llama-2-7B heads) has this
     form 3.5 x (256 new tokens) and 8.5 x (1024) SLOWER than a whole-prompt `context_attention_fwd` over all the tokens; against
     anything else it has not been measured.  It saves the prefix's projections, not attention time, and nothing picks it automatically."""
+    if kv_layer.dtype == torch.float8_e4m3fn:
+        raise NotImplementedError("prefill_with_cached_prefix over an fp8 KV pool is not implemented (fp8 pools serve the tree decode steps and the append of a plain prefill)")
     n1, Hq = q.shape[0], q.shape[1]
     if n1 == 0:
         return

@@ -77,9 +77,16 @@ def _prep(q, k_buffer, v_buffer, o, req_to_token, b_req_idx, b_start_loc, b_seq_
     return nq, Hq, Hkv, D, b_req_idx, b_start_loc, b_seq_len, int(total_num_tokens)
 
 
+def _refuse_fp8(pool_tensor, what: str) -> None:
+    if getattr(pool_tensor, "dtype", None) == torch.float8_e4m3fn:
+        raise NotImplementedError(f"{what}: the sequential comparator does not read an fp8 KV pool (fp8 pools serve the tree decode "
+                                  "operators, tree_attention_*_kv8)")
+
+
 @torch.inference_mode()
 def token_attention_fwd(q, k_buffer, v_buffer, o, req_to_token, b_req_idx, b_start_loc, b_seq_len, max_len_in_batch,
                         other_kv_index, total_num_tokens, att_m=None) -> None:
+    _refuse_fp8(k_buffer, "token_attention_fwd")
     nq, Hq, Hkv, D, b_req_idx, b_start_loc, b_seq_len, total = _prep(q, k_buffer, v_buffer, o, req_to_token, b_req_idx,
                                                                      b_start_loc, b_seq_len, total_num_tokens)
     stream = _stream_ptr(q)
@@ -98,6 +105,7 @@ def seq_append_attention(q, kv_layer, o, cache_loc, cache_k, cache_v, req_to_tok
                          total_num_tokens) -> None:
     """`store_kv_cache` + `token_attention_fwd` in one launch sequence (radix_attention_forward,
     deft_attention.py:153-188); kv_layer is one layer of the pool, [size, 2, Hkv, D] fp16 or bf16."""
+    _refuse_fp8(kv_layer, "seq_append_attention")
     k_buffer, v_buffer = kv_layer[:, 0], kv_layer[:, 1]
     nq, Hq, Hkv, D, b_req_idx, b_start_loc, b_seq_len, total = _prep(q, k_buffer, v_buffer, o, req_to_token, b_req_idx,
                                                                      b_start_loc, b_seq_len, total_num_tokens)

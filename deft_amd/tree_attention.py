@@ -20,10 +20,10 @@ from __future__ import annotations
 
 import torch
 
-from ._lib import DeftLibraryError, check, entry, lib, same_elem_dtype, tensor_version
+from ._lib import KV8_DTYPE, DeftLibraryError, check, entry, lib, same_elem_dtype, tensor_version
 
 __all__ = ["tree_attention_subtree_fwd", "tree_attention_fwd", "flatten_append_attention", "kv_append",
-           "flatten_stage1_partials"]
+           "flatten_stage1_partials", "tree_attention_subtree_fwd_kv8", "tree_attention_fwd_kv8", "kv_append_kv8"]
 
 
 def _stream_ptr(t: torch.Tensor) -> int:
@@ -389,3 +389,163 @@ def flatten_stage1_partials(query_states, key_buffer, value_buffer, block_q, blo
     check(lib.deft_flatten_read_partials(ws.data_ptr(), ws_bytes, NB, P, nq, Hq, Hkv, D, po.data_ptr(), pl.data_ptr(), st),
           "deft_flatten_read_partials")
     return po, pl
+
+
+# ---------------------------------------------------------------------------
+# fp8 KV pools: OCP e4m3fn codes (torch.float8_e4m3fn) with per-KV-head fp32 scales.  q / output / the new rows keep one 16-bit
+# element type; a stored code c of head h means float(c) * scale[h].  No fused append: kv_append_kv8, then the
+# operator -- two launches.
+# ---------------------------------------------------------------------------
+def _kv8_scale(scale, name: str, Hkv: int, device):
+    """Device pointer of a per-KV-head scale tensor (fp32, `Hkv` elements, on the pool's device), or None = all ones."""
+    if scale is None:
+        return None
+    if not isinstance(scale, torch.Tensor) or scale.dtype != torch.float32:
+        raise TypeError(f"{name} must be a float32 tensor of {Hkv} per-KV-head scales or None, got {getattr(scale, 'dtype', type(scale))}")
+    if scale.numel() != Hkv:
+        raise TypeError(f"{name} must hold one scale per KV head ({Hkv}), got {scale.numel()}")
+    if scale.device != device:
+        raise TypeError(f"{name} is on {scale.device} but the KV pool is on {device}")
+    if not scale.is_contiguous():
+        scale = scale.contiguous()
+    return scale
+
+
+def _check_qkv_kv8(query_states, key_buffer, value_buffer, output, k_scale, v_scale):
+    dtype = same_elem_dtype(query_states=query_states, output=output)
+    for name, t in (("key_buffer", key_buffer), ("value_buffer", value_buffer)):
+        if t.dtype != KV8_DTYPE:
+            raise TypeError(f"{name} must be {KV8_DTYPE} (an fp8 KV pool), got {t.dtype}")
+    for name, t in (("query_states", query_states), ("key_buffer", key_buffer), ("value_buffer", value_buffer), ("output", output)):
+        if t.dim() != 3 or t.stride(2) != 1:
+            raise ValueError(f"{name} must be [n, heads, head_dim] with a contiguous head_dim")
+    nq, Hq, D = query_states.shape
+    Hkv = key_buffer.shape[1]
+    ks = _kv8_scale(k_scale, "k_scale", Hkv, key_buffer.device)
+    vs = _kv8_scale(v_scale, "v_scale", Hkv, key_buffer.device)
+    for name, t in (("query_states", query_states), ("key_buffer", key_buffer), ("value_buffer", value_buffer), ("output", output)):
+        if not t.is_cuda:
+            raise DeftLibraryError(f"{name} must be a CUDA (ROCm) tensor; deft_amd has no CPU path")
+    if D != 128:
+        raise ValueError(f"fp8 KV pools are built for head_dim 128 only, got {D}")
+    if key_buffer.shape != value_buffer.shape or key_buffer.stride() != value_buffer.stride():
+        raise ValueError("key_buffer and value_buffer must have identical shape and strides")
+    if output.shape != query_states.shape:
+        raise ValueError("output must have the shape of query_states")
+    if key_buffer.stride(0) % 2:
+        raise ValueError("the fp8 pool's slot stride must be even")
+    return dtype, nq, Hq, Hkv, D, ks, vs
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+@torch.inference_mode()
+def tree_attention_subtree_fwd_kv8(query_states, key_buffer, value_buffer, output, block_len, block_q, block_q_cnts, block_q_offset,
+                                   block_bitmasks, block_kv, block_lens, k_scale=None, v_scale=None, scale=None) -> None:
+    """`tree_attention_subtree_fwd` (DeFT-Flatten) over an fp8 pool: key_buffer / value_buffer are float8_e4m3fn views
+    [slots, Hkv, 128], k_scale / v_scale fp32 tensors of Hkv per-head scales on the pool's device (None = ones), query_states and
+    output one 16-bit type.  `scale` (default 1/sqrt(head_dim)) is the softmax scale."""
+    _flatten_fwd_kv8(query_states, key_buffer, value_buffer, output, None, block_len, block_q, block_q_cnts, block_q_offset,
+                     block_bitmasks, block_kv, block_lens, k_scale, v_scale, scale)
+
+
+def _flatten_fwd_kv8(query_states, key_buffer, value_buffer, output, lse, block_len, block_q, block_q_cnts, block_q_offset,
+                     block_bitmasks, block_kv, block_lens, k_scale, v_scale, scale=None) -> None:
+    lse_args = _lse_args(lse, query_states)
+    dtype, nq, Hq, Hkv, D, ks, vs = _check_qkv_kv8(query_states, key_buffer, value_buffer, output, k_scale, v_scale)
+    _lse_on_device(lse)
+    if block_len != 128:
+        raise ValueError(f"block_len must be 128 (got {block_len})")
+    NB = block_q_cnts.shape[0]
+    P = block_q.shape[0]
+    md = [_i64(t, n) for t, n in ((block_q, "block_q"), (block_q_cnts, "block_q_cnts"),
+                                  (block_q_offset, "block_q_offset"), (block_bitmasks, "block_bitmasks"),
+                                  (block_kv, "block_kv"), (block_lens, "block_lens"))]
+    if block_kv.shape[0] != NB * 128 or block_bitmasks.shape[0] != NB * 128:
+        raise ValueError("block_kv / block_bitmasks must hold 128 entries per block")
+    ws_bytes = lib.deft_flatten_workspace_bytes(NB, P, nq, Hq, Hkv, D)
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=query_states.device)
+    stream = _stream_ptr(query_states)
+    # the plan addresses pool rows in 2-byte units: half the byte stride (tree_attention._flatten_plan caches per stride)
+    plan = _flatten_plan(md, NB, P, Hq, Hkv, (query_states.stride(0), query_states.stride(1)), key_buffer.stride(0) // 2, stream)
+    fn, fn_name = entry("deft_flatten_decode{}_kv8_lse" if lse_args else "deft_flatten_decode{}_kv8", dtype)
+    rc = fn(
+        query_states.data_ptr(), query_states.stride(0), query_states.stride(1),
+        key_buffer.data_ptr(), value_buffer.data_ptr(), key_buffer.stride(0), key_buffer.stride(1), _ptr(ks), _ptr(vs),
+        output.data_ptr(), output.stride(0), output.stride(1), *lse_args,
+        *[t.data_ptr() for t in md],
+        NB, P, nq, Hq, Hkv, D, 1.0 / (D ** 0.5) if scale is None else float(scale), plan.data_ptr(), ws.data_ptr(), ws_bytes, stream,
+    )
+    check(rc, fn_name)
+
+
+@torch.inference_mode()
+def tree_attention_fwd_kv8(query_states, key_buffer, value_buffer, output, KV_indices, KV_indices_offset, KV_len, KVMapQ_List,
+                           KVMapQ_List_Offset, KVMapQ_List_Len, k_scale=None, v_scale=None, scale=None) -> None:
+    """`tree_attention_fwd` (DeFT-Node) over an fp8 pool; arguments as tree_attention_subtree_fwd_kv8."""
+    _node_fwd_kv8(query_states, key_buffer, value_buffer, output, None, KV_indices, KV_indices_offset, KV_len, KVMapQ_List,
+                  KVMapQ_List_Offset, KVMapQ_List_Len, k_scale, v_scale, scale)
+
+
+def _node_fwd_kv8(query_states, key_buffer, value_buffer, output, lse, KV_indices, KV_indices_offset, KV_len, KVMapQ_List,
+                  KVMapQ_List_Offset, KVMapQ_List_Len, k_scale, v_scale, scale=None) -> None:
+    lse_args = _lse_args(lse, query_states)
+    dtype, nq, Hq, Hkv, D, ks, vs = _check_qkv_kv8(query_states, key_buffer, value_buffer, output, k_scale, v_scale)
+    _lse_on_device(lse)
+    NE = KV_indices_offset.shape[0]
+    P = KVMapQ_List.shape[0]
+    total_kv = KV_indices.shape[0]
+    md = [_i64(t, n) for t, n in ((KV_indices, "KV_indices"), (KV_indices_offset, "KV_indices_offset"),
+                                  (KV_len, "KV_len"), (KVMapQ_List, "KVMapQ_List"),
+                                  (KVMapQ_List_Offset, "KVMapQ_List_Offset"), (KVMapQ_List_Len, "KVMapQ_List_Len"))]
+    ws_bytes = lib.deft_node_workspace_bytes(NE, P, total_kv, nq, Hq, Hkv, D)
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=query_states.device)
+    stream = _stream_ptr(query_states)
+    plan = _node_plan(md, NE, P, total_kv, Hq, Hkv, (query_states.stride(0), query_states.stride(1)),
+                      key_buffer.stride(0) // 2, stream)
+    fn, fn_name = entry("deft_node_decode{}_kv8_lse" if lse_args else "deft_node_decode{}_kv8", dtype)
+    rc = fn(
+        query_states.data_ptr(), query_states.stride(0), query_states.stride(1),
+        key_buffer.data_ptr(), value_buffer.data_ptr(), key_buffer.stride(0), key_buffer.stride(1), _ptr(ks), _ptr(vs),
+        output.data_ptr(), output.stride(0), output.stride(1), *lse_args,
+        *[t.data_ptr() for t in md],
+        NE, P, total_kv, nq, Hq, Hkv, D, 1.0 / (D ** 0.5) if scale is None else float(scale), plan.data_ptr(), ws.data_ptr(), ws_bytes,
+        stream,
+    )
+    check(rc, fn_name)
+
+
+@torch.inference_mode()
+def kv_append_kv8(kv_layer: torch.Tensor, cache_loc: torch.Tensor, cache_k: torch.Tensor, cache_v: torch.Tensor,
+                  k_scale=None, v_scale=None) -> None:
+    """Quantising paged append: kv_layer[cache_loc, 0] = e4m3fn(clamp(cache_k / k_scale, -448, 448)) and the same for V, rounded to
+    nearest even, in one launch.  kv_layer is one layer of an fp8 pool, [size, 2, Hkv, D] float8_e4m3fn; cache_k / cache_v are the
+    new rows in fp16 or bf16 (one type); k_scale / v_scale fp32 [Hkv] on the pool's device, or None = ones."""
+    if kv_layer.dtype != KV8_DTYPE:
+        raise TypeError(f"kv_layer must be {KV8_DTYPE} (an fp8 KV pool), got {kv_layer.dtype}")
+    dtype = same_elem_dtype(cache_k=cache_k, cache_v=cache_v)
+    size, two, Hkv, D = kv_layer.shape
+    ks = _kv8_scale(k_scale, "k_scale", Hkv, kv_layer.device)
+    vs = _kv8_scale(v_scale, "v_scale", Hkv, kv_layer.device)
+    if not kv_layer.is_cuda:
+        raise DeftLibraryError("kv_append_kv8 needs a CUDA (ROCm) pool; deft_amd has no CPU path")
+    assert two == 2 and kv_layer.stride(3) == 1
+    n = cache_loc.shape[0]
+    k = cache_k.reshape(n, Hkv, D)
+    v = cache_v.reshape(n, Hkv, D)
+    if k.stride(2) != 1 or k.stride(1) != D:
+        k = k.contiguous()
+    if v.stride() != k.stride():
+        v = v.contiguous()
+        k = k.contiguous()
+    if cache_loc.dtype != torch.int32:
+        cache_loc = cache_loc.to(torch.int32)
+    cache_loc = cache_loc.to(kv_layer.device)
+    fn, fn_name = entry("deft_kv_append{}_kv8", dtype)
+    rc = fn(
+        kv_layer[:, 0].data_ptr(), kv_layer[:, 1].data_ptr(), kv_layer.stride(0), kv_layer.stride(2), _ptr(ks), _ptr(vs),
+        cache_loc.data_ptr(), k.data_ptr(), v.data_ptr(), k.stride(0), n, Hkv, D, _stream_ptr(kv_layer),
+    )
+    check(rc, fn_name)

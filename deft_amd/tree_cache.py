@@ -76,9 +76,13 @@ class KVCacheUpdater:
     def update(self, layer_id: int, cache_k: torch.Tensor, cache_v: torch.Tensor) -> None:
         assert self.token_to_kv_pool is not None
         assert self.cache_loc is not None
-        from .tree_attention import kv_append
+        from .tree_attention import kv_append, kv_append_kv8
 
-        kv_append(self.token_to_kv_pool.kv_data[layer_id], self.cache_loc, cache_k, cache_v)
+        pool = self.token_to_kv_pool
+        if getattr(pool, "is_fp8", False):  # an fp8 pool: the rows are quantised with the layer's per-head scales on their way in
+            kv_append_kv8(pool.kv_data[layer_id], self.cache_loc, cache_k, cache_v, pool.k_scale[layer_id], pool.v_scale[layer_id])
+            return
+        kv_append(pool.kv_data[layer_id], self.cache_loc, cache_k, cache_v)
 
 
 class _Slots(MutableSequence):

@@ -546,6 +546,129 @@ int deft_kv_append_bf16(
     const int32_t* cache_loc, const void* k_new, const void* v_new, int64_t new_stride_tok,
     int n, int Hkv, int D, void* stream);
 
+/* ---- fp8 KV pools (OCP e4m3fn) ------------------------------------------- */
+
+/*
+ * The K/V pool holds OCP e4m3fn codes (torch.float8_e4m3fn; NOT the fnuz format), one byte per element, in the same
+ * [slot][K|V][Hkv][D] layout; q, the new rows and out stay in a 16-bit element type T (the _f16 / _bf16 inside the name, as for the
+ * *_lse entry points: the names ENDING in _f16 / _bf16 stay the twelve of the plain surface).
+ *   k_scale, v_scale    per-KV-head fp32 scales [Hkv], DEVICE pointers (nothing reads them on the host, no sync); either may be
+ *                       NULL = all ones.  Finite and > 0: the caller guarantees it.
+ *   meaning of a code   a stored code c of head h is the real number float(c) * scale[h].  The conversion e4m3 -> T is exact; the
+ *                       scales never pass through a 16-bit rounding: k_scale[h] multiplies the fp32 softmax scale, v_scale[h] the
+ *                       fp32 result before a partial row is normalised.  Everything else is the 16-bit path's arithmetic (fp32 scores,
+ *                       probabilities rounded once to T, 16-bit matrix products, fp32 partial rows, the same merge).
+ *   strides             kv_stride_slot / kv_stride_head are in pool ELEMENTS = bytes.
+ *   geometry            head_dim 128 only (DEFT_EUNSUPPORTED otherwise: head_dim 64 / 32 / 16 are not built for fp8 pools); any
+ *                       Hkv, odd ones included; Hq / Hkv as for the plain calls.  The pool base and the slot stride must be 16-byte
+ *                       aligned, the head stride a multiple of 16, the slot stride even (DEFT_EINVAL).
+ *   plan                NULL (built per call into the workspace) or a plan from the plain deft_*_build_plan with
+ *                       kv_stride_slot = byte stride / 2 and cache_loc = NULL: a pool row is half as long, the records' byte
+ *                       offsets are then right as they stand.  There is NO fused append for fp8 pools: a plan built WITH a
+ *                       cache_loc (rows flagged as this step's new ones) is invalid for these entry points.  Append with
+ *                       deft_kv_append_*_kv8 first.
+ *   sizes               deft_*_workspace_bytes and deft_*_plan_bytes do not depend on the pool's type.
+ * The *_kv8 parameter lists are the plain siblings' with `k_scale, v_scale` directly behind kv_stride_head; the *_kv8_lse forms add
+ * `lse, lse_stride_tok, lse_stride_head` behind the out strides like every *_lse entry point, and their (out, lse) combine with any
+ * other state through deft_merge_*_states.
+ */
+int deft_flatten_decode_f16_kv8(
+    const void* q, int64_t q_stride_tok, int64_t q_stride_head,
+    const void* k_base, const void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head,
+    const float* k_scale, const float* v_scale,
+    void* out, int64_t o_stride_tok, int64_t o_stride_head,
+    const int64_t* block_q, const int64_t* block_q_cnts, const int64_t* block_q_offset,
+    const int64_t* block_bitmasks, const int64_t* block_kv, const int64_t* block_lens,
+    int NB, int P, int nq, int Hq, int Hkv, int D, float scale,
+    const void* plan, void* workspace, size_t workspace_bytes, void* stream);
+/* bfloat16 twin of deft_flatten_decode_f16_kv8: the same contract with bfloat16 q / out */
+int deft_flatten_decode_bf16_kv8(
+    const void* q, int64_t q_stride_tok, int64_t q_stride_head,
+    const void* k_base, const void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head,
+    const float* k_scale, const float* v_scale,
+    void* out, int64_t o_stride_tok, int64_t o_stride_head,
+    const int64_t* block_q, const int64_t* block_q_cnts, const int64_t* block_q_offset,
+    const int64_t* block_bitmasks, const int64_t* block_kv, const int64_t* block_lens,
+    int NB, int P, int nq, int Hq, int Hkv, int D, float scale,
+    const void* plan, void* workspace, size_t workspace_bytes, void* stream);
+int deft_flatten_decode_f16_kv8_lse(
+    const void* q, int64_t q_stride_tok, int64_t q_stride_head,
+    const void* k_base, const void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head,
+    const float* k_scale, const float* v_scale,
+    void* out, int64_t o_stride_tok, int64_t o_stride_head,
+    float* lse, int64_t lse_stride_tok, int64_t lse_stride_head,
+    const int64_t* block_q, const int64_t* block_q_cnts, const int64_t* block_q_offset,
+    const int64_t* block_bitmasks, const int64_t* block_kv, const int64_t* block_lens,
+    int NB, int P, int nq, int Hq, int Hkv, int D, float scale,
+    const void* plan, void* workspace, size_t workspace_bytes, void* stream);
+/* bfloat16 twin of deft_flatten_decode_f16_kv8_lse */
+int deft_flatten_decode_bf16_kv8_lse(
+    const void* q, int64_t q_stride_tok, int64_t q_stride_head,
+    const void* k_base, const void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head,
+    const float* k_scale, const float* v_scale,
+    void* out, int64_t o_stride_tok, int64_t o_stride_head,
+    float* lse, int64_t lse_stride_tok, int64_t lse_stride_head,
+    const int64_t* block_q, const int64_t* block_q_cnts, const int64_t* block_q_offset,
+    const int64_t* block_bitmasks, const int64_t* block_kv, const int64_t* block_lens,
+    int NB, int P, int nq, int Hq, int Hkv, int D, float scale,
+    const void* plan, void* workspace, size_t workspace_bytes, void* stream);
+int deft_node_decode_f16_kv8(
+    const void* q, int64_t q_stride_tok, int64_t q_stride_head,
+    const void* k_base, const void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head,
+    const float* k_scale, const float* v_scale,
+    void* out, int64_t o_stride_tok, int64_t o_stride_head,
+    const int64_t* node_kv, const int64_t* node_kv_offset, const int64_t* node_kv_len,
+    const int64_t* node_q, const int64_t* node_q_offset, const int64_t* node_q_len,
+    int NE, int P, int64_t total_kv, int nq, int Hq, int Hkv, int D, float scale,
+    const void* plan, void* workspace, size_t workspace_bytes, void* stream);
+/* bfloat16 twin of deft_node_decode_f16_kv8 */
+int deft_node_decode_bf16_kv8(
+    const void* q, int64_t q_stride_tok, int64_t q_stride_head,
+    const void* k_base, const void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head,
+    const float* k_scale, const float* v_scale,
+    void* out, int64_t o_stride_tok, int64_t o_stride_head,
+    const int64_t* node_kv, const int64_t* node_kv_offset, const int64_t* node_kv_len,
+    const int64_t* node_q, const int64_t* node_q_offset, const int64_t* node_q_len,
+    int NE, int P, int64_t total_kv, int nq, int Hq, int Hkv, int D, float scale,
+    const void* plan, void* workspace, size_t workspace_bytes, void* stream);
+int deft_node_decode_f16_kv8_lse(
+    const void* q, int64_t q_stride_tok, int64_t q_stride_head,
+    const void* k_base, const void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head,
+    const float* k_scale, const float* v_scale,
+    void* out, int64_t o_stride_tok, int64_t o_stride_head,
+    float* lse, int64_t lse_stride_tok, int64_t lse_stride_head,
+    const int64_t* node_kv, const int64_t* node_kv_offset, const int64_t* node_kv_len,
+    const int64_t* node_q, const int64_t* node_q_offset, const int64_t* node_q_len,
+    int NE, int P, int64_t total_kv, int nq, int Hq, int Hkv, int D, float scale,
+    const void* plan, void* workspace, size_t workspace_bytes, void* stream);
+/* bfloat16 twin of deft_node_decode_f16_kv8_lse */
+int deft_node_decode_bf16_kv8_lse(
+    const void* q, int64_t q_stride_tok, int64_t q_stride_head,
+    const void* k_base, const void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head,
+    const float* k_scale, const float* v_scale,
+    void* out, int64_t o_stride_tok, int64_t o_stride_head,
+    float* lse, int64_t lse_stride_tok, int64_t lse_stride_head,
+    const int64_t* node_kv, const int64_t* node_kv_offset, const int64_t* node_kv_len,
+    const int64_t* node_q, const int64_t* node_q_offset, const int64_t* node_q_len,
+    int NE, int P, int64_t total_kv, int nq, int Hq, int Hkv, int D, float scale,
+    const void* plan, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Quantising paged append: for i < n, head h, k_base[cache_loc[i]][h][:] = e4m3fn(clamp(float(k_new[i][h][:]) / k_scale[h], -448, 448))
+ * rounded to nearest even (subnormal codes produced, +-0 preserved, NaN -> a NaN code), and the same for v.  The division is fp32
+ * division.  New rows are Hkv*D elements of T with token stride new_stride_tok and head stride D; pool strides in bytes; D a
+ * multiple of 8; every pointer and stride 16-byte aligned (the pool's: 8).  Touches nothing but the named slots. */
+int deft_kv_append_f16_kv8(
+    void* k_base, void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head,
+    const float* k_scale, const float* v_scale,
+    const int32_t* cache_loc, const void* k_new, const void* v_new, int64_t new_stride_tok,
+    int n, int Hkv, int D, void* stream);
+/* bfloat16 twin of deft_kv_append_f16_kv8 */
+int deft_kv_append_bf16_kv8(
+    void* k_base, void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head,
+    const float* k_scale, const float* v_scale,
+    const int32_t* cache_loc, const void* k_new, const void* v_new, int64_t new_stride_tok,
+    int n, int Hkv, int D, void* stream);
+
 /* ---- stage-level entry points (benchmarks / profiling) ------------------- */
 
 /* Measurement aid, not on the product path: ONE launch of `workgroups` x 256 threads that reads `bytes` bytes at `base` (16-byte
