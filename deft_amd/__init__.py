@@ -16,8 +16,12 @@ from .session import DecodeSession, FlattenDecodeSession  # noqa: F401
 from .states import (  # noqa: F401
     cached_prefix_blocks,
     context_attention_fwd_lse,
+    flatten_append_attention_kv8,
+    flatten_append_attention_kv8_lse,
     flatten_append_attention_lse,
     merge_attention_states,
+    node_append_attention_kv8,
+    node_append_attention_kv8_lse,
     node_append_attention_lse,
     prefill_with_cached_prefix,
     tree_attention_fwd_kv8_lse,

@@ -162,6 +162,21 @@ for _f, _at in (("deft_flatten_decode", len(_QKV)), ("deft_node_decode", len(_QK
             getattr(lib, _f + _s + "_kv8_lse").argtypes = _with_lse(_kv8, len(_QKV + _SCALES + _OUT))
             getattr(lib, _f + _s + "_kv8_lse").restype = C.c_int
 
+# The fused quantising append over an fp8 pool (tree_attention.py *_append_attention_kv8): the 16-bit *_decode_append* siblings'
+# arguments with the same two pointers behind kv_stride_head.  A tuple of its own: KV8_ENTRY_POINTS stays the five above.
+KV8_APPEND_ENTRY_POINTS = ("deft_flatten_decode_append{}_kv8", "deft_flatten_decode_append{}_kv8_lse", "deft_node_decode_append{}_kv8",
+                           "deft_node_decode_append{}_kv8_lse")
+for _f in ("deft_flatten_decode_append", "deft_node_decode_append"):
+    _plain = list(getattr(lib, _f + "_f16").argtypes)
+    for _s in ("_f16", "_bf16"):
+        if not hasattr(lib, _f + _s + "_kv8"):  # (DEFT_AMD_LIB may name an older build: `entry` says so)
+            continue
+        _kv8 = _plain[:len(_QKV)] + _SCALES + _plain[len(_QKV):]
+        getattr(lib, _f + _s + "_kv8").argtypes = _kv8
+        getattr(lib, _f + _s + "_kv8").restype = C.c_int
+        getattr(lib, _f + _s + "_kv8_lse").argtypes = _with_lse(_kv8, len(_QKV + _SCALES + _OUT))
+        getattr(lib, _f + _s + "_kv8_lse").restype = C.c_int
+
 _SUFFIX = {torch.float16: "_f16", torch.bfloat16: "_bf16"}
 ELEM_DTYPES = tuple(_SUFFIX)
 
@@ -268,7 +283,7 @@ EXPORTED = (
     "deft_prefill_f16", "deft_rope_qk_f16", "deft_seq_plan_bytes", "deft_seq_workspace_bytes", "deft_seq_build_plan", "deft_seq_decode_f16", "deft_seq_decode_append_f16",
     "deft_kv_append_f16", "deft_probe_stream_read", "deft_md_build", "deft_md_sizes", "deft_md_fetch", "deft_md_free",
     "deft_tree_create",
-) + tuple(_f + "_bf16" for _f in ELEM_ENTRY_POINTS) + tuple(_f.format(_s) for _f in STATE_ENTRY_POINTS + KV8_ENTRY_POINTS for _s in ("_f16", "_bf16")) + tuple(_TREE_FUNCS)
+) + tuple(_f + "_bf16" for _f in ELEM_ENTRY_POINTS) + tuple(_f.format(_s) for _f in STATE_ENTRY_POINTS + KV8_ENTRY_POINTS + KV8_APPEND_ENTRY_POINTS for _s in ("_f16", "_bf16")) + tuple(_TREE_FUNCS)
 
 _ERR_NAMES = {-1: "DEFT_EINVAL", -2: "DEFT_EUNSUPPORTED", -3: "DEFT_EHIP", -4: "DEFT_EWORKSPACE"}
 

@@ -618,7 +618,8 @@ static int num_cus() {
 }
 enum : unsigned { ATTR_NP = 4,  // (bits 0-1, 8-11: the head_dim 64 / 32 / 16 kernels)
                   ATTR_UNITS = 8, ATTR_NODE_UNITS = 16, ATTR_PREFILL = 32, ATTR_TREE = 64, ATTR_NP_ROPE = 128, ATTR_NP_T = 8192, ATTR_NP_ROPE_T = 16384, ATTR_NP_HD2 = 32768, ATTR_NP_HD2_T = 65536, ATTR_PREFILL_64 = 1u << 17, ATTR_NP_DYN = 1u << 18, ATTR_NP_ROPE_DYN = 1u << 19, ATTR_NP_HD2_DYN = 1u << 20, ATTR_PREFILL_LSE = 1u << 21, ATTR_PREFILL_64_LSE = 1u << 22,
-                  ATTR_KV8 = 1u << 23, ATTR_KV8_T = 1u << 24, ATTR_KV8_DYN = 1u << 25 };
+                  ATTR_KV8 = 1u << 23, ATTR_KV8_T = 1u << 24, ATTR_KV8_DYN = 1u << 25,
+                  ATTR_KV8_APP = 1u << 26, ATTR_KV8_APP_T = 1u << 27, ATTR_KV8_APP_DYN = 1u << 28 };
 template <class T>
 constexpr uint64_t attr_bit(unsigned bit) { return std::is_same<T, BF16>::value ? (uint64_t)bit << 32 : (uint64_t)bit; }
 static int raise_lds(const void* fn, int bytes, uint64_t bit, const char* what) {  // idempotent; races are harmless
@@ -1312,18 +1313,22 @@ static int kv_append_impl(void* k_base, void* v_base, int64_t kv_stride_slot, in
 
 // ---------------------------------------------------------------------------
 // fp8 KV pools (stage1_kv8.h): the *_kv8 entry points.  Plan builders, workspace, merge are the 16-bit path's own; only stage 1
-// and the append differ.  There is no fused append: the plans are built with cache_loc = NULL.
+// and the append differ.  The plain entry points have no fused append (their plans are built with cache_loc = NULL); the
+// *_decode_append_*_kv8 ones launch the APP instantiations over a plan that flags this step's rows.
 // ---------------------------------------------------------------------------
-template <class T>
-static int launch_stage1_kv8(const Stage1Params& p, int64_t unit_cap, const PlanView& pv, const Kv8& s8, hipStream_t stream, int nq) {
+// `ap` (APP): this step's new rows; `pool_ss`: the pool's slot stride in bytes (p.kv_ss is the plan builders' 2-byte unit).
+template <class T, bool APP = false>
+static int launch_stage1_kv8(const Stage1Params& p, int64_t unit_cap, const PlanView& pv, const Kv8& s8, hipStream_t stream, int nq,
+                             const AppendArgs* ap = nullptr, int64_t pool_ss = 0) {
     using SM = Kv8Smem;
+    using Params = std::conditional_t<APP, Kv8AppParams, Kv8Params>;
     // the launch rules of launch_stage1_np (cache policy, DYN, grid cap, mirrored order), which depend on the plan and the geometry alone
     const bool nt = p.G > 1 || (int64_t)nq <= 1024;
     const bool small_gqa = unit_cap * p.Hkv <= 16LL * num_cus();
     const bool dyn = nt && p.G > 1 && (small_gqa || (int64_t)nq * p.G > 160);
-    void (*kernel)(Kv8Params) = dyn ? &stage1_kv8_kernel<T, true, true> : nt ? &stage1_kv8_kernel<T, true> : &stage1_kv8_kernel<T, false>;
-    const int rc = raise_lds(reinterpret_cast<const void*>(kernel), SM::BYTES, attr_bit<T>(dyn ? ATTR_KV8_DYN : nt ? ATTR_KV8 : ATTR_KV8_T),
-                             "stage1_kv8");
+    void (*kernel)(Params) = dyn ? &stage1_kv8_kernel<T, true, true, APP> : nt ? &stage1_kv8_kernel<T, true, false, APP> : &stage1_kv8_kernel<T, false, false, APP>;
+    const unsigned bit = APP ? (dyn ? ATTR_KV8_APP_DYN : nt ? ATTR_KV8_APP : ATTR_KV8_APP_T) : (dyn ? ATTR_KV8_DYN : nt ? ATTR_KV8 : ATTR_KV8_T);
+    const int rc = raise_lds(reinterpret_cast<const void*>(kernel), SM::BYTES, attr_bit<T>(bit), "stage1_kv8");
     if (rc) return rc;
     if (unit_cap <= 0) return DEFT_OK;
     int64_t grid = unit_cap * p.Hkv;
@@ -1336,7 +1341,7 @@ static int launch_stage1_kv8(const Stage1Params& p, int64_t unit_cap, const Plan
     if (grid > cap_wgs) grid = cap_wgs;
     const int gx = knob("DEFT_NP_GRID", 0);  // (experiments build, tests: a tiny grid = many rounds of the item loop)
     if (gx > 0 && grid > gx) grid = gx;
-    Kv8Params kp{};
+    Params kp{};
     kp.s = p;
     kp.plan = pv.records;
     kp.hdr = pv.hdr;
@@ -1344,16 +1349,28 @@ static int launch_stage1_kv8(const Stage1Params& p, int64_t unit_cap, const Plan
     kp.fast_n = 2 * num_cus();
     kp.k_scale = s8.k_scale;
     kp.v_scale = s8.v_scale;
+    if constexpr (APP) {
+        kp.cache_loc = ap->cache_loc;
+        kp.k_new = ap->k_new;
+        kp.v_new = ap->v_new;
+        kp.new_st = ap->new_st;
+        kp.pool_ss = pool_ss;
+        kp.n_new = ap->n_new;
+    }
     hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(256), SM::BYTES, stream, kp);
     return check_launch("stage1 kv8 launch");
 }
 
 template <class T>
-static int flatten_decode_kv8_impl(const Tensors& t, const Kv8& s8, const FlattenMd& md, const Scratch& sc) {
+static int flatten_decode_kv8_impl(const Tensors& t, const Kv8& s8, const FlattenMd& md, const Scratch& sc, const AppendArgs* ap = nullptr) {
     int rc = s8.check(t);
     if (rc) return rc;
     rc = t.check();
     if (rc) return rc;
+    if (ap) {  // (the order of flatten_decode_impl)
+        rc = ap->check(t.Hkv, t.D);
+        if (rc) return rc;
+    }
     rc = sc.check();
     if (rc) return rc;
     rc = md.check();
@@ -1373,16 +1390,16 @@ static int flatten_decode_kv8_impl(const Tensors& t, const Kv8& s8, const Flatte
         pv = plan_view(const_cast<void*>(sc.plan), cap, md.P);
     } else {
         pv = plan_view(ws.plan, cap, md.P);
-        rc = launch_plan(p, md.NB, pv, AppendArgs(), sc.st());
+        rc = launch_plan(p, md.NB, pv, ap ? *ap : AppendArgs(), sc.st());  // (a plan with `ap` flags this step's rows)
         if (rc) return rc;
     }
-    rc = launch_stage1_kv8<T>(p, cap, pv, s8, sc.st(), t.nq);
+    rc = ap ? launch_stage1_kv8<T, true>(p, cap, pv, s8, sc.st(), t.nq, ap, t.kv_ss) : launch_stage1_kv8<T>(p, cap, pv, s8, sc.st(), t.nq);
     if (rc) return rc;
     return launch_merge<T>(t.D, ws, &pv, pv.row_q, md.P, t.out, t.o_st, t.o_sh, t.nq, t.Hq, t.G(), sc.st(), t.lse, t.lse_st, t.lse_sh);
 }
 
 template <class T>
-static int node_decode_kv8_impl(const Tensors& t, const Kv8& s8, const NodeMd& md, const Scratch& sc) {
+static int node_decode_kv8_impl(const Tensors& t, const Kv8& s8, const NodeMd& md, const Scratch& sc, const AppendArgs* ap = nullptr) {
     int rc = s8.check(t);
     if (rc) return rc;
     rc = t.check();
@@ -1391,6 +1408,10 @@ static int node_decode_kv8_impl(const Tensors& t, const Kv8& s8, const NodeMd& m
     if (rc) return rc;
     rc = sc.check();
     if (rc) return rc;
+    if (ap) {  // (the order of node_decode_impl)
+        rc = ap->check(t.Hkv, t.D);
+        if (rc) return rc;
+    }
     const int G = t.G();
     const int64_t tiles = md.tiles(), rows = md.rows();
     const Workspace ws = carve(sc.workspace, t.Hq, t.D, rows, tiles, md.plan(nullptr, G).bytes);
@@ -1407,10 +1428,10 @@ static int node_decode_kv8_impl(const Tensors& t, const Kv8& s8, const NodeMd& m
         pv = md.plan(const_cast<void*>(sc.plan), G);
     } else {
         pv = md.plan(ws.plan, G);
-        rc = launch_node_plan(p, md.NE, rows, pv, AppendArgs(), sc.st());
+        rc = launch_node_plan(p, md.NE, rows, pv, ap ? *ap : AppendArgs(), sc.st());
         if (rc) return rc;
     }
-    rc = launch_stage1_kv8<T>(p, tiles * G, pv, s8, sc.st(), t.nq);
+    rc = ap ? launch_stage1_kv8<T, true>(p, tiles * G, pv, s8, sc.st(), t.nq, ap, t.kv_ss) : launch_stage1_kv8<T>(p, tiles * G, pv, s8, sc.st(), t.nq);
     if (rc) return rc;
     return launch_merge<T>(t.D, ws, &pv, pv.row_q, rows, t.out, t.o_st, t.o_sh, t.nq, t.Hq, G, sc.st(), t.lse, t.lse_st, t.lse_sh);
 }
@@ -1930,6 +1951,49 @@ DEFT_STATE_TWINS(node_decode, _kv8_lse, (const void* q, int64_t q_stride_tok, in
             node_q_offset, const int64_t* node_q_len, int NE, int P, int64_t total_kv, int nq, int Hq, int Hkv, int D, float
             scale, const void* plan, void* workspace, size_t workspace_bytes, void* stream),
            { return node_decode_kv8_impl<T>(TENSORS_LSE, KV8, NODE_MD, SCRATCH); })
+// The fused quantising append: the 16-bit *_decode_append* parameter lists with the two scales behind kv_stride_head.
+DEFT_STATE_TWINS(flatten_decode_append, _kv8, (const void* q, int64_t q_stride_tok, int64_t q_stride_head, void* k_base, void* v_base,
+            int64_t kv_stride_slot, int64_t kv_stride_head, const float* k_scale, const float* v_scale, void* out, int64_t
+            o_stride_tok, int64_t o_stride_head, const int64_t* block_q, const int64_t* block_q_cnts, const int64_t* block_q_offset,
+            const int64_t* block_bitmasks, const int64_t* block_kv, const int64_t* block_lens, int NB, int P, int nq, int Hq, int
+            Hkv, int D, float scale, const int32_t* cache_loc, const void* k_new, const void* v_new, int64_t new_stride_tok, int
+            n_new, const void* plan, void* workspace, size_t workspace_bytes, void* stream), {
+    AppendArgs ap;
+    if (int rc = make_append(ap, APPEND)) return rc;
+    return flatten_decode_kv8_impl<T>(TENSORS, KV8, FLATTEN_MD, SCRATCH, &ap);
+})
+DEFT_STATE_TWINS(flatten_decode_append, _kv8_lse, (const void* q, int64_t q_stride_tok, int64_t q_stride_head, void* k_base, void* v_base,
+            int64_t kv_stride_slot, int64_t kv_stride_head, const float* k_scale, const float* v_scale, void* out, int64_t
+            o_stride_tok, int64_t o_stride_head, float* lse, int64_t lse_stride_tok, int64_t lse_stride_head, const int64_t*
+            block_q, const int64_t* block_q_cnts, const int64_t* block_q_offset, const int64_t* block_bitmasks, const int64_t*
+            block_kv, const int64_t* block_lens, int NB, int P, int nq, int Hq, int Hkv, int D, float scale, const int32_t*
+            cache_loc, const void* k_new, const void* v_new, int64_t new_stride_tok, int n_new, const void* plan, void* workspace,
+            size_t workspace_bytes, void* stream), {
+    AppendArgs ap;
+    if (int rc = make_append(ap, APPEND)) return rc;
+    return flatten_decode_kv8_impl<T>(TENSORS_LSE, KV8, FLATTEN_MD, SCRATCH, &ap);
+})
+DEFT_STATE_TWINS(node_decode_append, _kv8, (const void* q, int64_t q_stride_tok, int64_t q_stride_head, void* k_base, void* v_base,
+            int64_t kv_stride_slot, int64_t kv_stride_head, const float* k_scale, const float* v_scale, void* out, int64_t
+            o_stride_tok, int64_t o_stride_head, const int64_t* node_kv, const int64_t* node_kv_offset, const int64_t* node_kv_len,
+            const int64_t* node_q, const int64_t* node_q_offset, const int64_t* node_q_len, int NE, int P, int64_t total_kv, int nq,
+            int Hq, int Hkv, int D, float scale, const int32_t* cache_loc, const void* k_new, const void* v_new, int64_t
+            new_stride_tok, int n_new, const void* plan, void* workspace, size_t workspace_bytes, void* stream), {
+    AppendArgs ap;
+    if (int rc = make_append(ap, APPEND)) return rc;
+    return node_decode_kv8_impl<T>(TENSORS, KV8, NODE_MD, SCRATCH, &ap);
+})
+DEFT_STATE_TWINS(node_decode_append, _kv8_lse, (const void* q, int64_t q_stride_tok, int64_t q_stride_head, void* k_base, void* v_base,
+            int64_t kv_stride_slot, int64_t kv_stride_head, const float* k_scale, const float* v_scale, void* out, int64_t
+            o_stride_tok, int64_t o_stride_head, float* lse, int64_t lse_stride_tok, int64_t lse_stride_head, const int64_t*
+            node_kv, const int64_t* node_kv_offset, const int64_t* node_kv_len, const int64_t* node_q, const int64_t* node_q_offset,
+            const int64_t* node_q_len, int NE, int P, int64_t total_kv, int nq, int Hq, int Hkv, int D, float scale, const int32_t*
+            cache_loc, const void* k_new, const void* v_new, int64_t new_stride_tok, int n_new, const void* plan, void* workspace,
+            size_t workspace_bytes, void* stream), {
+    AppendArgs ap;
+    if (int rc = make_append(ap, APPEND)) return rc;
+    return node_decode_kv8_impl<T>(TENSORS_LSE, KV8, NODE_MD, SCRATCH, &ap);
+})
 DEFT_STATE_TWINS(kv_append, _kv8, (void* k_base, void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head, const float* k_scale,
             const float* v_scale, const int32_t* cache_loc, const void* k_new, const void* v_new, int64_t new_stride_tok, int n,
             int Hkv, int D, void* stream),

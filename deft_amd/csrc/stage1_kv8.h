@@ -1,4 +1,5 @@
-// Stage 1 over an fp8 KV pool (OCP e4m3fn codes, one byte per element, per-KV-head fp32 scales), and the quantising paged append.
+// Stage 1 over an fp8 KV pool (OCP e4m3fn codes, one byte per element, per-KV-head fp32 scales), the quantising paged append, and the
+// two fused (APP).
 //
 // Included by deft_kernels.hip after stage1_np.h, whose structure this kernel keeps (read that header first): one workgroup per chunk
 // of KV tiles, four waves that are each their own pipeline -- wave w stages keys [32w, 32w+32) of a tile into its private LDS slices
@@ -34,8 +35,25 @@
 //            16t + 8 + 4h + e - 4): P^T is the B operand as it stands.  A 32-lane half touches 8 rows x 32 bytes: with the XOR
 //            above the 32 eight-byte pieces cover one 256-byte bank row exactly.
 //
-// The fused append of the 16-bit kernel is NOT carried over (a NEW row would have to be read from 16-bit k_new into an 8-bit slice):
-// the plans this kernel takes are built with cache_loc = NULL, so no record has bit 63 of a row offset set.
+// The fused quantising append (APP = true; the *_decode_append_*_kv8 entry points).  With APP = false the plans are built with
+// cache_loc = NULL, no record has bit 63 of a row offset set, and the kernel is the one it was before the parameter existed.  With APP:
+//   * pool write: workgroup W-1-bid takes new rows W-1-bid, +W, ...: one thread per 16-byte piece of T -> 8 codes through quant_fp8x8
+//     with the head's scale (kv8_append_kernel's function: the same bytes), one 8-byte store to K and to V at cache_loc * pool_ss
+//     BYTES.  Nobody reads those pool rows in this launch.
+//   * a record built with cache_loc flags this step's rows with bit 63 of rowoff; the low bits are the row's byte offset in the 16-bit
+//     k_new / v_new.  Such a row is 256 bytes of T, not 128 bytes of codes: no DMA can stage it.  load_rowoff takes one ballot over the
+//     sign of the wave's 32 offsets; a slice without a flagged row runs the instruction stream it always ran.  Otherwise (wave-uniform
+//     slow path) all LPT DMA instructions are issued with every lane active, the flagged lanes pointed at the head's first pool row --
+//     the counted s_waitcnt vmcnt sees what it always sees -- and at the top of iteration i (rowoff[] still holds tile i's offsets, K(i)
+//     and V(i) are issued) every lane loads 32 bytes of T, drains vmcnt(0), quantises, and a flagged lane overwrites the 16
+//     bytes its DMA lane wrote (ldsK / ldsV + i * 1024 + lane * 16: chunk kchunk_b / vchunk_b of the row, the swizzle sits in the source
+//     chunk); s_waitcnt lgkmcnt(0) before the fragment reads.  The codes that reach the MFMA are the codes the pool receives: the call
+//     equals kv_append + the APP = false kernel bit for bit.
+//   * hazards: the ds_write is ordered behind the DMA write to the same bytes by the vmcnt(0) that covers that DMA, by nothing else; no
+//     exec-masked LDS-DMA; every lane loads (the unflagged ones a piece of new row 0) so that no piece is conditionally defined -- such
+//     values are live across the whole tile loop and spill; K pieces, then V pieces: both at once do not fit beside the accumulators.
+//   * cost: on a decode step the new row is the last key of every leaf, so the slow path sits at the end of
+//     every leaf's work item; it is faster than the separate append on ToT-50 and slower on the north-star step.
 #pragma once
 
 namespace deft {
@@ -50,6 +68,16 @@ struct Kv8Params {
     int fast_n;            // workgroups < fast_n request tile 0's offsets before anything else
     const float* k_scale;  // [Hkv] fp32 on the device, or null = all ones
     const float* v_scale;
+};
+
+// APP: this step's new rows, for the fused quantising append
+struct Kv8AppParams : Kv8Params {
+    const int32_t* cache_loc;  // [n_new] pool slots
+    const e16* k_new;          // [n_new] rows of T, new_st elements apart, heads contiguous ([Hkv][128])
+    const e16* v_new;
+    int64_t new_st;
+    int64_t pool_ss;           // the pool's slot stride in BYTES (s.kv_ss is the plan builders' 2-byte unit)
+    int n_new;
 };
 
 // two e4m3 codes (word HI of w) -> two elements of T, exact
@@ -72,6 +100,30 @@ __device__ __forceinline__ typename T::vec8 cvt_fp8x8(uint32_t lo, uint32_t hi) 
     return u.v;
 }
 
+// eight elements of T (one 16-byte piece) -> eight e4m3 codes: the quantisation of kv8_append_kernel (below) and of the fused append
+//   code = RNE_e4m3fn(clamp(float(x) / scale[head], -448, +448)); NaN -> a NaN code; +-0 preserved; subnormal codes produced
+template <class T>
+__device__ __forceinline__ intx2 quant_fp8x8(uintx4 x, float scale) {
+    union {
+        uintx4 u;
+        typename T::vec8 h8;
+    } in;
+    in.u = x;
+    float f[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const float y = T::to_float(in.h8[e]) / scale;  // true fp32 division
+        // the clamp is explicit (v_med3_f32 returns a finite bound for a NaN input: NaN passes by)
+        f[e] = (y != y) ? y : __builtin_amdgcn_fmed3f(y, -448.f, 448.f);
+    }
+    intx2 r;
+    r[0] = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], 0, false);
+    r[0] = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], r[0], true);
+    r[1] = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], 0, false);
+    r[1] = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], r[1], true);
+    return r;
+}
+
 struct Kv8Smem {
     // per wave 16 KB: its K slice [32][128 B] at +0, its V slice at +4096; in the epilogue the whole 16 KB is the wave's parked
     // O [32 query rows][128 floats] -- nobody else ever touched it, hence ONE barrier as in the 16-bit kernel
@@ -88,8 +140,9 @@ struct Kv8Smem {
 
 // NT: K / V rows arrive by non-temporal LDS-DMA; DYN (with NT; GQA launches): the cache policy is the chunk leader's (desc[6]) and a
 // capped grid may take its further items in mirrored order -- the rules of stage1_np_kernel, decided by the same host code.
-template <class T, bool NT, bool DYN = false>
-__global__ __launch_bounds__(256, 2) void stage1_kv8_kernel(Kv8Params np) {
+// APP: the fused quantising append (header comment).  With APP = false nothing below differs from the kernel without the parameter.
+template <class T, bool NT, bool DYN = false, bool APP = false>
+__global__ __launch_bounds__(256, 2) void stage1_kv8_kernel(std::conditional_t<APP, Kv8AppParams, Kv8Params> np) {
     using scalar = typename T::scalar;
     using vec8 = typename T::vec8;
     constexpr int D = 128;
@@ -108,6 +161,25 @@ __global__ __launch_bounds__(256, 2) void stage1_kv8_kernel(Kv8Params np) {
     const int bid = blockIdx.x;
     const int W = (int)gridDim.x;
     const int HP = p.Hkv;
+
+    // ---- fused quantising append (the scheme of stage1_np_kernel): new row j enters the pool through workgroup (grid-1-j) % grid, one
+    //      16-byte piece of T per thread -> 8 codes, the bytes kv8_append_kernel writes.  Nobody reads those pool rows in this launch:
+    //      the plan flags them and the tile loop takes them from k_new / v_new.
+    if constexpr (APP) {
+        char* const kw = const_cast<char*>(reinterpret_cast<const char*>(p.k));
+        char* const vw = const_cast<char*>(reinterpret_cast<const char*>(p.v));
+        for (int copy_job = W - 1 - bid; copy_job < np.n_new; copy_job += W) {
+            const int64_t dst = (int64_t)np.cache_loc[copy_job] * np.pool_ss;
+            for (int i = tid; i < HP * (D / 8); i += 256) {
+                const int hd = i / (D / 8), ch = i - hd * (D / 8);
+                const int64_t so = (int64_t)copy_job * np.new_st + hd * D + ch * 8;
+                const int64_t d_o = dst + (int64_t)hd * p.kv_sh + ch * 8;  // bytes
+                const float ks = np.k_scale ? np.k_scale[hd] : 1.f, vs = np.v_scale ? np.v_scale[hd] : 1.f;
+                *reinterpret_cast<intx2*>(kw + d_o) = quant_fp8x8<T>(*reinterpret_cast<const uintx4*>(np.k_new + so), ks);
+                *reinterpret_cast<intx2*>(vw + d_o) = quant_fp8x8<T>(*reinterpret_cast<const uintx4*>(np.v_new + so), vs);
+            }
+        }
+    }
 
     int NI = 0x7fffffff;  // leaders x heads, read with the first item's descriptor
     int item = bid, round = 0;
@@ -151,8 +223,11 @@ __global__ __launch_bounds__(256, 2) void stage1_kv8_kernel(Kv8Params np) {
     const int qpos = l & 15, qkey = l >> 4;
 
     const char *kb_pool = nullptr, *vb_pool = nullptr;  // per work item (KV head)
+    constexpr int64_t NEW_ROW = (int64_t)1 << 63;
 
+    bool temporal = false;  // (wave-uniform, per work item; DYN)
     int64_t rowoff[LPT];
+    bool has_new = false;  // (APP, wave-uniform) some row of the slice whose offsets `rowoff` holds is one of this step's new rows
     auto issue_aux = [&](int i, int slot) {  // 2 DMA: this wave's 32 row offsets; its 32 key masks | the 32 q offsets
         const char* rec = rec_of(i);
         dma4(rec + PLAN_ROWOFF + 32 * w * 8 + 4 * l, aux0 + (uint32_t)slot * SM::AUX_SLOT);
@@ -163,10 +238,31 @@ __global__ __launch_bounds__(256, 2) void stage1_kv8_kernel(Kv8Params np) {
         const int64_t* ro = reinterpret_cast<const int64_t*>(smem + aux0 + slot * SM::AUX_SLOT);
 #pragma unroll
         for (int i = 0; i < LPT; ++i) rowoff[i] = ro[8 * i + drow];
+        if constexpr (APP) {  // lane k looks at the sign of row k's offset: one ballot per slice (stage1_np_kernel)
+            const int32_t hi = reinterpret_cast<const int32_t*>(ro)[2 * (l & 31) + 1];
+            has_new = __builtin_amdgcn_ballot_w64(hi < 0) != 0ull;
+        }
     };
-    bool temporal = false;  // (wave-uniform, per work item; DYN)
+    // (APP) the slice holds a new row: a new row is 256 bytes of T, not 128 bytes of codes, so no DMA can stage it.  Every DMA is
+    // issued all the same, with every lane active -- the counted waits see the operations they always see -- and the lanes of a new
+    // row fetch a piece of the head's first pool row instead; the slow path at the top of the tile's iteration overwrites what they staged.
+    auto issue_slice_new = [&](const char* pool, const int (&chunk_b)[2], uint32_t lds) __attribute__((always_inline)) {
+        const bool nt = NT && !(DYN && temporal);
+#pragma unroll
+        for (int i = 0; i < LPT; ++i) {
+            const char* src = pool + (rowoff[i] < 0 ? (int64_t)0 : rowoff[i]) + chunk_b[i & 1];
+            if (nt) dma16nt(src, lds + (uint32_t)i * 1024u);
+            else dma16(src, lds + (uint32_t)i * 1024u);
+        }
+    };
     auto issue_k = [&]() __attribute__((always_inline)) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's reads of the slice being overwritten
+        if constexpr (APP) {
+            if (has_new) {
+                issue_slice_new(kb_pool, kchunk_b, ldsK);
+                return;
+            }
+        }
         if (NT && !(DYN && temporal)) {
 #pragma unroll
             for (int i = 0; i < LPT; ++i) dma16nt(kb_pool + rowoff[i] + kchunk_b[i & 1], ldsK + (uint32_t)i * 1024u);
@@ -177,6 +273,12 @@ __global__ __launch_bounds__(256, 2) void stage1_kv8_kernel(Kv8Params np) {
     };
     auto issue_v = [&]() __attribute__((always_inline)) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        if constexpr (APP) {
+            if (has_new) {
+                issue_slice_new(vb_pool, vchunk_b, ldsV);
+                return;
+            }
+        }
         if (NT && !(DYN && temporal)) {
 #pragma unroll
             for (int i = 0; i < LPT; ++i) dma16nt(vb_pool + rowoff[i] + vchunk_b[i & 1], ldsV + (uint32_t)i * 1024u);
@@ -264,6 +366,38 @@ __global__ __launch_bounds__(256, 2) void stage1_kv8_kernel(Kv8Params np) {
     for (int i = 0; i < n; ++i) {
         const bool has1 = i + 1 < n, has2 = i + 2 < n;
         const int slot = i & 1;
+        if constexpr (APP) {
+            // ---- slow path (wave-uniform): tile i holds a new row.  `rowoff` still holds tile i's offsets and K(i), V(i) are both
+            //      issued.  A DMA lane of a new row owns the 16-byte piece at lane * 16 of its instruction's 1 KB: 16 codes, chunk
+            //      kchunk_b / vchunk_b of the row (the swizzle sits in the SOURCE chunk), i.e. 32 bytes of T at twice that offset.  It
+            //      loads them, drains vmcnt(0) -- its loads and every DMA into the two slices, so the ds_write below is ordered behind
+            //      the DMA write to the same bytes by the wait that covers that DMA --, quantises with the pool write's function and
+            //      scales (the codes that reach the MFMA are the codes the pool receives) and overwrites its piece.
+            if (has_new) {
+                // (K, then V: sixteen pieces of T in flight per lane at a time -- thirty-two do not fit next to the accumulators)
+                auto fix = [&](const char* base, const int (&chunk_b)[2], float scale, uint32_t lds) __attribute__((always_inline)) {
+                    uintx4 pn[LPT][2];
+#pragma unroll
+                    for (int ii = 0; ii < LPT; ++ii) {  // (every lane loads -- the others the same piece of new row 0 -- and only the store is predicated)
+                        const char* src = base + (rowoff[ii] < 0 ? rowoff[ii] & ~NEW_ROW : (int64_t)0) + 2 * chunk_b[ii & 1];
+                        pn[ii][0] = *reinterpret_cast<const uintx4*>(src);
+                        pn[ii][1] = *reinterpret_cast<const uintx4*>(src + 16);
+                    }
+                    wait_vm<0>();
+#pragma unroll
+                    for (int ii = 0; ii < LPT; ++ii)
+                        if (rowoff[ii] < 0) {
+                            const intx2 c0 = quant_fp8x8<T>(pn[ii][0], scale), c1 = quant_fp8x8<T>(pn[ii][1], scale);
+                            const uintx4 cq = {(uint32_t)c0[0], (uint32_t)c0[1], (uint32_t)c1[0], (uint32_t)c1[1]};
+                            *reinterpret_cast<uintx4*>(smem + lds + ii * 1024 + l * 16) = cq;
+                        }
+                };
+                // (the head's 256 bytes of T inside a new row; the bases are formed here, not kept in registers across the tile loop)
+                fix(reinterpret_cast<const char*>(np.k_new) + kvh * (D * 2), kchunk_b, ksc, ldsK);
+                fix(reinterpret_cast<const char*>(np.v_new) + kvh * (D * 2), vchunk_b, vsc, ldsV);
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the pieces are in LDS before any fragment read of this wave
+            }
+        }
         // ---- K(i) (and Q) landed: younger than it are aux(i+1) [2] and V(i) [LPT] -----------------------
         if (has1) wait_vm<LPT + 2>();
         else wait_vm<LPT>();
@@ -430,31 +564,8 @@ __global__ __launch_bounds__(256, 2) void stage1_kv8_kernel(Kv8Params np) {
 }
 
 // ---------------------------------------------------------------------------
-// quantising paged append: one 16-byte piece of a new row (8 elements of T) per thread -> 8 codes, one 8-byte store
-//   code = RNE_e4m3fn(clamp(float(x) / scale[head], -448, +448)); NaN -> a NaN code; +-0 preserved; subnormal codes produced
+// quantising paged append: one 16-byte piece of a new row (8 elements of T) per thread -> 8 codes (quant_fp8x8), one 8-byte store
 // ---------------------------------------------------------------------------
-template <class T>
-__device__ __forceinline__ intx2 quant_fp8x8(uintx4 x, float scale) {
-    union {
-        uintx4 u;
-        typename T::vec8 h8;
-    } in;
-    in.u = x;
-    float f[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const float y = T::to_float(in.h8[e]) / scale;  // true fp32 division
-        // the clamp is explicit (v_med3_f32 returns a finite bound for a NaN input: NaN passes by)
-        f[e] = (y != y) ? y : __builtin_amdgcn_fmed3f(y, -448.f, 448.f);
-    }
-    intx2 r;
-    r[0] = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], 0, false);
-    r[0] = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], r[0], true);
-    r[1] = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], 0, false);
-    r[1] = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], r[1], true);
-    return r;
-}
-
 template <class T>
 __global__ __launch_bounds__(256) void kv8_append_kernel(uint8_t* k_base, uint8_t* v_base, int64_t kv_ss, int64_t kv_sh,
                                                           const int32_t* cache_loc, const e16* k_new, const e16* v_new, int64_t new_st,

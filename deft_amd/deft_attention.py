@@ -23,8 +23,8 @@ from ._lib import DeftLibraryError, check, entry, lib, same_elem_dtype, tensor_v
 from .forward_mode import ForwardMode, InputMetadata
 from .context_attention import context_attention_fwd
 from .token_attention import seq_append_attention, token_attention_fwd
-from .tree_attention import (flatten_append_attention, node_append_attention, tree_attention_fwd, tree_attention_fwd_kv8,
-                             tree_attention_subtree_fwd, tree_attention_subtree_fwd_kv8)
+from .tree_attention import (_flatten_append_kv8, _node_append_kv8, flatten_append_attention, node_append_attention,
+                             tree_attention_fwd, tree_attention_fwd_kv8, tree_attention_subtree_fwd, tree_attention_subtree_fwd_kv8)
 from .tree_cache import get_global_tree_metadata
 
 
@@ -412,12 +412,19 @@ class DeFTAttention(nn.Module):
             f"Unsupported forward mode: {mode} (deft_amd covers TREE_DECODE_FLATTEN, TREE_DECODE_NODE, EXTEND, DECODE and PREFILL with paged KV)"
         )
 
+    # fp8 pools, the two tree decode modes: the quantising append as a launch of its own (False) or inside the stage-1 launch (True:
+    # flatten_append_attention_kv8 / node_append_attention_kv8, the same outputs and pool bytes bit for bit).  False by measurement: the
+    # fused form gains 1.75 us per layer on ToT-50 and LOSES 4.97 us on the north-star step (DESIGN section 6e,
+    # profiles/kv8_fused_cost.txt); tools/kv8_ab.py flips it per instance to time both.
+    kv8_fused_append = False
+
     def kv8_forward(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, input_metadata: InputMetadata,
                     rotary_emb=None, positions: torch.Tensor = None, fuse_rope: bool = None) -> torch.Tensor:
         """`forward` over an fp8 KV pool (TokenToKVPool(dtype=torch.float8_e4m3fn)): the two tree decode modes (node_chunk included:
         it is Node metadata) and PREFILL.  Two launches per layer -- the quantising append (store_kv_cache), then the kv8 operator with
-        the layer's per-head scales; a given rotary embedding runs first with its own launch.  There is no fused append, no fused
-        rotary embedding, no extend step and no sequential comparator for fp8 pools: those are refused, never misread as 16-bit."""
+        the layer's per-head scales -- or, with `kv8_fused_append`, the fused operators; a given rotary embedding runs first with its
+        own launch.  There is no fused rotary embedding, no extend step and no sequential comparator for fp8 pools: those are
+        refused, never misread as 16-bit."""
         mode = input_metadata.forward_mode
         pool = input_metadata.token_to_kv_pool
         if fuse_rope:
@@ -443,10 +450,22 @@ class DeFTAttention(nn.Module):
         _check_query_tile(md)
         Hq, Hkv, D = self.tp_q_head_num, self.tp_k_head_num, self.head_dim
         o = torch.empty((q.shape[0], Hq * D), dtype=q.dtype, device=q.device)
-        self.store_kv_cache(k.view(-1, Hkv, D), v.view(-1, Hkv, D), input_metadata)
         q3, o3 = q.view(-1, Hq, D), o.view(-1, Hq, D)
-        kb, vb = pool.get_key_buffer(self.layer_id), pool.get_value_buffer(self.layer_id)
         ks, vs = pool.k_scale[self.layer_id], pool.v_scale[self.layer_id]
+        updater = input_metadata.kv_updater
+        if self.kv8_fused_append and updater is not None and updater.cache_loc is not None and updater.token_to_kv_pool is pool:
+            # the quantising append inside the stage-1 launch: outputs and pool bytes are the two-launch path's, bit for bit
+            kv_layer = pool.kv_data[self.layer_id]
+            k3, v3 = k.view(-1, Hkv, D), v.view(-1, Hkv, D)
+            if mode == ForwardMode.TREE_DECODE_FLATTEN:
+                _flatten_append_kv8(q3, kv_layer, o3, None, updater.cache_loc, k3, v3, md.block_len, md.block_q, md.block_q_cnts,
+                                    md.block_q_offset, md.block_bitmasks, md.block_kv, md.block_lens, ks, vs)
+            else:
+                _node_append_kv8(q3, kv_layer, o3, None, updater.cache_loc, k3, v3, md.node_kv, md.node_kv_offset, md.node_kv_len,
+                                 md.node_q, md.node_q_offset, md.node_q_len, ks, vs)
+            return o
+        self.store_kv_cache(k.view(-1, Hkv, D), v.view(-1, Hkv, D), input_metadata)
+        kb, vb = pool.get_key_buffer(self.layer_id), pool.get_value_buffer(self.layer_id)
         if mode == ForwardMode.TREE_DECODE_FLATTEN:
             tree_attention_subtree_fwd_kv8(q3, kb, vb, o3, md.block_len, md.block_q, md.block_q_cnts, md.block_q_offset,
                                            md.block_bitmasks, md.block_kv, md.block_lens, k_scale=ks, v_scale=vs)

@@ -19,12 +19,13 @@ import torch
 
 from ._lib import DeftLibraryError, check, entry, same_elem_dtype
 from .context_attention import _prefill
-from .tree_attention import (_flatten_append, _flatten_fwd, _flatten_fwd_kv8, _lse_args, _node_append, _node_fwd, _node_fwd_kv8,
-                             _stream_ptr, kv_append)
+from .tree_attention import (_flatten_append, _flatten_append_kv8, _flatten_fwd, _flatten_fwd_kv8, _lse_args, _node_append,
+                             _node_append_kv8, _node_fwd, _node_fwd_kv8, _stream_ptr, kv_append)
 
 __all__ = ["tree_attention_subtree_fwd_lse", "tree_attention_fwd_lse", "flatten_append_attention_lse", "node_append_attention_lse",
            "context_attention_fwd_lse", "merge_attention_states", "cached_prefix_blocks", "prefill_with_cached_prefix",
-           "tree_attention_subtree_fwd_kv8_lse", "tree_attention_fwd_kv8_lse"]
+           "tree_attention_subtree_fwd_kv8_lse", "tree_attention_fwd_kv8_lse", "flatten_append_attention_kv8",
+           "flatten_append_attention_kv8_lse", "node_append_attention_kv8", "node_append_attention_kv8_lse"]
 
 
 def _need(lse):
@@ -80,6 +81,43 @@ def node_append_attention_lse(query_states, kv_layer, output, lse, cache_loc, ca
     """`node_append_attention` (paged append fused into Node attention) that also writes lse[q, h]."""
     _node_append(query_states, kv_layer, output, _need(lse), cache_loc, cache_k, cache_v, KV_indices, KV_indices_offset, KV_len,
                  KVMapQ_List, KVMapQ_List_Offset, KVMapQ_List_Len)
+
+
+# ---- fp8 pools: the quantising append fused into the tree decode ------------------------------------------------------------------------
+# `flatten_append_attention` / `node_append_attention` over one layer of an fp8 pool ([slots, 2, Hkv, 128] float8_e4m3fn): cache_k /
+# cache_v (16-bit, the type of query_states and output) enter slots cache_loc as the codes kv_append_kv8 writes and the attention
+# already sees them -- output, lse and every pool byte are bit-identical to kv_append_kv8 followed by the *_kv8 operator, in one
+# stage-1 launch less.  k_scale / v_scale: fp32 [Hkv] on the pool's device or None = ones; `scale`: the softmax scale.
+@torch.inference_mode()
+def flatten_append_attention_kv8(query_states, kv_layer, output, cache_loc, cache_k, cache_v, block_len, block_q, block_q_cnts,
+                                 block_q_offset, block_bitmasks, block_kv, block_lens, k_scale=None, v_scale=None, scale=None) -> None:
+    """`kv_append_kv8` + `tree_attention_subtree_fwd_kv8` (DeFT-Flatten over an fp8 pool) in one launch sequence."""
+    _flatten_append_kv8(query_states, kv_layer, output, None, cache_loc, cache_k, cache_v, block_len, block_q, block_q_cnts,
+                        block_q_offset, block_bitmasks, block_kv, block_lens, k_scale, v_scale, scale)
+
+
+@torch.inference_mode()
+def flatten_append_attention_kv8_lse(query_states, kv_layer, output, lse, cache_loc, cache_k, cache_v, block_len, block_q, block_q_cnts,
+                                     block_q_offset, block_bitmasks, block_kv, block_lens, k_scale=None, v_scale=None, scale=None) -> None:
+    """`flatten_append_attention_kv8` that also writes lse[q, h]."""
+    _flatten_append_kv8(query_states, kv_layer, output, _need(lse), cache_loc, cache_k, cache_v, block_len, block_q, block_q_cnts,
+                        block_q_offset, block_bitmasks, block_kv, block_lens, k_scale, v_scale, scale)
+
+
+@torch.inference_mode()
+def node_append_attention_kv8(query_states, kv_layer, output, cache_loc, cache_k, cache_v, KV_indices, KV_indices_offset, KV_len,
+                              KVMapQ_List, KVMapQ_List_Offset, KVMapQ_List_Len, k_scale=None, v_scale=None, scale=None) -> None:
+    """`kv_append_kv8` + `tree_attention_fwd_kv8` (DeFT-Node over an fp8 pool) in one launch sequence."""
+    _node_append_kv8(query_states, kv_layer, output, None, cache_loc, cache_k, cache_v, KV_indices, KV_indices_offset, KV_len,
+                     KVMapQ_List, KVMapQ_List_Offset, KVMapQ_List_Len, k_scale, v_scale, scale)
+
+
+@torch.inference_mode()
+def node_append_attention_kv8_lse(query_states, kv_layer, output, lse, cache_loc, cache_k, cache_v, KV_indices, KV_indices_offset,
+                                  KV_len, KVMapQ_List, KVMapQ_List_Offset, KVMapQ_List_Len, k_scale=None, v_scale=None, scale=None) -> None:
+    """`node_append_attention_kv8` that also writes lse[q, h]."""
+    _node_append_kv8(query_states, kv_layer, output, _need(lse), cache_loc, cache_k, cache_v, KV_indices, KV_indices_offset, KV_len,
+                     KVMapQ_List, KVMapQ_List_Offset, KVMapQ_List_Len, k_scale, v_scale, scale)
 
 
 @torch.inference_mode()

@@ -393,8 +393,8 @@ def flatten_stage1_partials(query_states, key_buffer, value_buffer, block_q, blo
 
 # ---------------------------------------------------------------------------
 # fp8 KV pools: OCP e4m3fn codes (torch.float8_e4m3fn) with per-KV-head fp32 scales.  q / output / the new rows keep one 16-bit
-# element type; a stored code c of head h means float(c) * scale[h].  No fused append: kv_append_kv8, then the
-# operator -- two launches.
+# element type; a stored code c of head h means float(c) * scale[h].  kv_append_kv8, then the operator, is two
+# stage-1-side launches; the *_append_attention_kv8 operators (deft_amd/states.py, bodies at the end of this file) fuse them.
 # ---------------------------------------------------------------------------
 def _kv8_scale(scale, name: str, Hkv: int, device):
     """Device pointer of a per-KV-head scale tensor (fp32, `Hkv` elements, on the pool's device), or None = all ones."""
@@ -547,5 +547,105 @@ def kv_append_kv8(kv_layer: torch.Tensor, cache_loc: torch.Tensor, cache_k: torc
     rc = fn(
         kv_layer[:, 0].data_ptr(), kv_layer[:, 1].data_ptr(), kv_layer.stride(0), kv_layer.stride(2), _ptr(ks), _ptr(vs),
         cache_loc.data_ptr(), k.data_ptr(), v.data_ptr(), k.stride(0), n, Hkv, D, _stream_ptr(kv_layer),
+    )
+    check(rc, fn_name)
+
+
+# ---- the fused quantising append: kv_append_kv8 + the kv8 operator in one stage-1 launch (public names in deft_amd/states.py) -------
+def _check_append_kv8(query_states, kv_layer, output, cache_loc, cache_k, cache_v, k_scale, v_scale):
+    """Types first (a TypeError names the wrong argument), then the device, then shapes; returns what the call needs."""
+    if not isinstance(kv_layer, torch.Tensor) or kv_layer.dtype != KV8_DTYPE:
+        raise TypeError(f"kv_layer must be {KV8_DTYPE} (one layer of an fp8 KV pool), got {getattr(kv_layer, 'dtype', type(kv_layer))}")
+    dtype = same_elem_dtype(query_states=query_states, output=output, cache_k=cache_k, cache_v=cache_v)
+    if kv_layer.dim() != 4 or kv_layer.shape[1] != 2 or kv_layer.stride(3) != 1:
+        raise ValueError("kv_layer must be [slots, 2, Hkv, head_dim] with a contiguous head_dim")
+    Hkv = kv_layer.shape[2]
+    ks = _kv8_scale(k_scale, "k_scale", Hkv, kv_layer.device)
+    vs = _kv8_scale(v_scale, "v_scale", Hkv, kv_layer.device)
+    key_buffer, value_buffer = kv_layer[:, 0], kv_layer[:, 1]
+    for name, t in (("query_states", query_states), ("output", output)):
+        if t.dim() != 3 or t.stride(2) != 1:
+            raise ValueError(f"{name} must be [n, heads, head_dim] with a contiguous head_dim")
+    for name, t in (("query_states", query_states), ("kv_layer", kv_layer), ("output", output), ("cache_k", cache_k), ("cache_v", cache_v)):
+        if not t.is_cuda:
+            raise DeftLibraryError(f"{name} must be a CUDA (ROCm) tensor; deft_amd has no CPU path")
+    nq, Hq, D = query_states.shape
+    if D != 128 or kv_layer.shape[3] != D:
+        raise ValueError(f"fp8 KV pools are built for head_dim 128 only, got {D} (pool: {kv_layer.shape[3]})")
+    if output.shape != query_states.shape:
+        raise ValueError("output must have the shape of query_states")
+    if key_buffer.stride(0) % 2:
+        raise ValueError("the fp8 pool's slot stride must be even")
+    n = cache_loc.shape[0]
+    k = cache_k.reshape(n, Hkv, D)
+    v = cache_v.reshape(n, Hkv, D)
+    if k.stride(2) != 1 or k.stride(1) != D:
+        k = k.contiguous()
+    if v.stride() != k.stride():
+        k, v = k.contiguous(), v.contiguous()
+    if cache_loc.dtype != torch.int32 or not cache_loc.is_cuda:
+        cache_loc = cache_loc.to(device=query_states.device, dtype=torch.int32)
+    return dtype, nq, Hq, Hkv, D, ks, vs, key_buffer, value_buffer, cache_loc, k, v, n
+
+
+def _flatten_append_kv8(query_states, kv_layer, output, lse, cache_loc, cache_k, cache_v, block_len, block_q, block_q_cnts,
+                        block_q_offset, block_bitmasks, block_kv, block_lens, k_scale, v_scale, scale=None) -> None:
+    lse_args = _lse_args(lse, query_states)
+    dtype, nq, Hq, Hkv, D, ks, vs, key_buffer, value_buffer, cache_loc, k, v, n = _check_append_kv8(
+        query_states, kv_layer, output, cache_loc, cache_k, cache_v, k_scale, v_scale)
+    _lse_on_device(lse)
+    if block_len != 128:
+        raise ValueError(f"block_len must be 128 (got {block_len})")
+    NB, P = block_q_cnts.shape[0], block_q.shape[0]
+    md = [_i64(t, n_) for t, n_ in ((block_q, "block_q"), (block_q_cnts, "block_q_cnts"),
+                                    (block_q_offset, "block_q_offset"), (block_bitmasks, "block_bitmasks"),
+                                    (block_kv, "block_kv"), (block_lens, "block_lens"))]
+    if block_kv.shape[0] != NB * 128 or block_bitmasks.shape[0] != NB * 128:
+        raise ValueError("block_kv / block_bitmasks must hold 128 entries per block")
+    ws_bytes = lib.deft_flatten_workspace_bytes(NB, P, nq, Hq, Hkv, D)
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=query_states.device)
+    stream = _stream_ptr(query_states)
+    # the plan addresses pool rows in 2-byte units (half the byte stride) and flags this step's rows: their offsets are bytes of k_new
+    plan = _flatten_plan(md, NB, P, Hq, Hkv, (query_states.stride(0), query_states.stride(1)), key_buffer.stride(0) // 2, stream,
+                         cache_loc=cache_loc, new_stride=k.stride(0))
+    fn, fn_name = entry("deft_flatten_decode_append{}_kv8_lse" if lse_args else "deft_flatten_decode_append{}_kv8", dtype)
+    rc = fn(
+        query_states.data_ptr(), query_states.stride(0), query_states.stride(1),
+        key_buffer.data_ptr(), value_buffer.data_ptr(), key_buffer.stride(0), key_buffer.stride(1), _ptr(ks), _ptr(vs),
+        output.data_ptr(), output.stride(0), output.stride(1), *lse_args,
+        *[t.data_ptr() for t in md],
+        NB, P, nq, Hq, Hkv, D, 1.0 / (D ** 0.5) if scale is None else float(scale),
+        cache_loc.data_ptr(), k.data_ptr(), v.data_ptr(), k.stride(0), n,
+        plan.data_ptr(), ws.data_ptr(), ws_bytes, stream,
+    )
+    check(rc, fn_name)
+
+
+def _node_append_kv8(query_states, kv_layer, output, lse, cache_loc, cache_k, cache_v, KV_indices, KV_indices_offset, KV_len,
+                     KVMapQ_List, KVMapQ_List_Offset, KVMapQ_List_Len, k_scale, v_scale, scale=None) -> None:
+    lse_args = _lse_args(lse, query_states)
+    dtype, nq, Hq, Hkv, D, ks, vs, key_buffer, value_buffer, cache_loc, k, v, n = _check_append_kv8(
+        query_states, kv_layer, output, cache_loc, cache_k, cache_v, k_scale, v_scale)
+    _lse_on_device(lse)
+    NE = KV_indices_offset.shape[0]
+    P = KVMapQ_List.shape[0]
+    total_kv = KV_indices.shape[0]
+    md = [_i64(t, n_) for t, n_ in ((KV_indices, "KV_indices"), (KV_indices_offset, "KV_indices_offset"),
+                                    (KV_len, "KV_len"), (KVMapQ_List, "KVMapQ_List"),
+                                    (KVMapQ_List_Offset, "KVMapQ_List_Offset"), (KVMapQ_List_Len, "KVMapQ_List_Len"))]
+    ws_bytes = lib.deft_node_workspace_bytes(NE, P, total_kv, nq, Hq, Hkv, D)
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=query_states.device)
+    stream = _stream_ptr(query_states)
+    plan = _node_plan(md, NE, P, total_kv, Hq, Hkv, (query_states.stride(0), query_states.stride(1)),
+                      key_buffer.stride(0) // 2, stream, cache_loc=cache_loc, new_stride=k.stride(0))
+    fn, fn_name = entry("deft_node_decode_append{}_kv8_lse" if lse_args else "deft_node_decode_append{}_kv8", dtype)
+    rc = fn(
+        query_states.data_ptr(), query_states.stride(0), query_states.stride(1),
+        key_buffer.data_ptr(), value_buffer.data_ptr(), key_buffer.stride(0), key_buffer.stride(1), _ptr(ks), _ptr(vs),
+        output.data_ptr(), output.stride(0), output.stride(1), *lse_args,
+        *[t.data_ptr() for t in md],
+        NE, P, total_kv, nq, Hq, Hkv, D, 1.0 / (D ** 0.5) if scale is None else float(scale),
+        cache_loc.data_ptr(), k.data_ptr(), v.data_ptr(), k.stride(0), n,
+        plan.data_ptr(), ws.data_ptr(), ws_bytes, stream,
     )
     check(rc, fn_name)

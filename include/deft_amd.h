@@ -564,9 +564,9 @@ int deft_kv_append_bf16(
  *                       aligned, the head stride a multiple of 16, the slot stride even (DEFT_EINVAL).
  *   plan                NULL (built per call into the workspace) or a plan from the plain deft_*_build_plan with
  *                       kv_stride_slot = byte stride / 2 and cache_loc = NULL: a pool row is half as long, the records' byte
- *                       offsets are then right as they stand.  There is NO fused append for fp8 pools: a plan built WITH a
- *                       cache_loc (rows flagged as this step's new ones) is invalid for these entry points.  Append with
- *                       deft_kv_append_*_kv8 first.
+ *                       offsets are then right as they stand.  These entry points append nothing: a plan built WITH a
+ *                       cache_loc (rows flagged as this step's new ones) is invalid for them.  Append with
+ *                       deft_kv_append_*_kv8 first, or call the *_decode_append_*_kv8 entry points below.
  *   sizes               deft_*_workspace_bytes and deft_*_plan_bytes do not depend on the pool's type.
  * The *_kv8 parameter lists are the plain siblings' with `k_scale, v_scale` directly behind kv_stride_head; the *_kv8_lse forms add
  * `lse, lse_stride_tok, lse_stride_head` behind the out strides like every *_lse entry point, and their (out, lse) combine with any
@@ -651,6 +651,108 @@ int deft_node_decode_bf16_kv8_lse(
     const int64_t* node_kv, const int64_t* node_kv_offset, const int64_t* node_kv_len,
     const int64_t* node_q, const int64_t* node_q_offset, const int64_t* node_q_len,
     int NE, int P, int64_t total_kv, int nq, int Hq, int Hkv, int D, float scale,
+    const void* plan, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * The fused quantising append: deft_kv_append_*_kv8 and the *_decode_*_kv8 call in ONE stage-1 launch.  The parameter lists are the
+ * 16-bit *_decode_append_* siblings' with `k_scale, v_scale` directly behind kv_stride_head.  For i < n_new the new row k_new[i] /
+ * v_new[i] (Hkv * 128 elements of T, token stride new_stride_tok, 16-byte aligned) enters pool slot cache_loc[i] as the codes
+ * deft_kv_append_*_kv8 writes, and the attention already sees it: a tile that holds one of this step's rows takes it from k_new /
+ * v_new, quantised by the same function with the same scales, so out, lse and every pool byte are BIT-IDENTICAL to
+ * deft_kv_append_*_kv8 followed by the plain *_kv8 call.  k_new, v_new and cache_loc are all required (DEFT_EINVAL), also with
+ * n_new = 0.
+ *   plan                NULL (built per call, with this cache_loc) or a plan from deft_*_build_plan with kv_stride_slot = byte
+ *                       stride / 2 and THIS step's cache_loc, n_new and new_stride_tok: the contract of the 16-bit append entry
+ *                       points.  A plan built without cache_loc is invalid here (the attention would read the slots' old bytes).
+ * Everything else -- geometry, alignment, scales, sizes -- as for the *_kv8 entry points above.
+ */
+int deft_flatten_decode_append_f16_kv8(
+    const void* q, int64_t q_stride_tok, int64_t q_stride_head,
+    void* k_base, void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head,
+    const float* k_scale, const float* v_scale,
+    void* out, int64_t o_stride_tok, int64_t o_stride_head,
+    const int64_t* block_q, const int64_t* block_q_cnts, const int64_t* block_q_offset,
+    const int64_t* block_bitmasks, const int64_t* block_kv, const int64_t* block_lens,
+    int NB, int P, int nq, int Hq, int Hkv, int D, float scale,
+    const int32_t* cache_loc, const void* k_new, const void* v_new, int64_t new_stride_tok, int n_new,
+    const void* plan, void* workspace, size_t workspace_bytes, void* stream);
+/* bfloat16 twin of deft_flatten_decode_append_f16_kv8 */
+int deft_flatten_decode_append_bf16_kv8(
+    const void* q, int64_t q_stride_tok, int64_t q_stride_head,
+    void* k_base, void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head,
+    const float* k_scale, const float* v_scale,
+    void* out, int64_t o_stride_tok, int64_t o_stride_head,
+    const int64_t* block_q, const int64_t* block_q_cnts, const int64_t* block_q_offset,
+    const int64_t* block_bitmasks, const int64_t* block_kv, const int64_t* block_lens,
+    int NB, int P, int nq, int Hq, int Hkv, int D, float scale,
+    const int32_t* cache_loc, const void* k_new, const void* v_new, int64_t new_stride_tok, int n_new,
+    const void* plan, void* workspace, size_t workspace_bytes, void* stream);
+int deft_flatten_decode_append_f16_kv8_lse(
+    const void* q, int64_t q_stride_tok, int64_t q_stride_head,
+    void* k_base, void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head,
+    const float* k_scale, const float* v_scale,
+    void* out, int64_t o_stride_tok, int64_t o_stride_head,
+    float* lse, int64_t lse_stride_tok, int64_t lse_stride_head,
+    const int64_t* block_q, const int64_t* block_q_cnts, const int64_t* block_q_offset,
+    const int64_t* block_bitmasks, const int64_t* block_kv, const int64_t* block_lens,
+    int NB, int P, int nq, int Hq, int Hkv, int D, float scale,
+    const int32_t* cache_loc, const void* k_new, const void* v_new, int64_t new_stride_tok, int n_new,
+    const void* plan, void* workspace, size_t workspace_bytes, void* stream);
+/* bfloat16 twin of deft_flatten_decode_append_f16_kv8_lse */
+int deft_flatten_decode_append_bf16_kv8_lse(
+    const void* q, int64_t q_stride_tok, int64_t q_stride_head,
+    void* k_base, void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head,
+    const float* k_scale, const float* v_scale,
+    void* out, int64_t o_stride_tok, int64_t o_stride_head,
+    float* lse, int64_t lse_stride_tok, int64_t lse_stride_head,
+    const int64_t* block_q, const int64_t* block_q_cnts, const int64_t* block_q_offset,
+    const int64_t* block_bitmasks, const int64_t* block_kv, const int64_t* block_lens,
+    int NB, int P, int nq, int Hq, int Hkv, int D, float scale,
+    const int32_t* cache_loc, const void* k_new, const void* v_new, int64_t new_stride_tok, int n_new,
+    const void* plan, void* workspace, size_t workspace_bytes, void* stream);
+int deft_node_decode_append_f16_kv8(
+    const void* q, int64_t q_stride_tok, int64_t q_stride_head,
+    void* k_base, void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head,
+    const float* k_scale, const float* v_scale,
+    void* out, int64_t o_stride_tok, int64_t o_stride_head,
+    const int64_t* node_kv, const int64_t* node_kv_offset, const int64_t* node_kv_len,
+    const int64_t* node_q, const int64_t* node_q_offset, const int64_t* node_q_len,
+    int NE, int P, int64_t total_kv, int nq, int Hq, int Hkv, int D, float scale,
+    const int32_t* cache_loc, const void* k_new, const void* v_new, int64_t new_stride_tok, int n_new,
+    const void* plan, void* workspace, size_t workspace_bytes, void* stream);
+/* bfloat16 twin of deft_node_decode_append_f16_kv8 */
+int deft_node_decode_append_bf16_kv8(
+    const void* q, int64_t q_stride_tok, int64_t q_stride_head,
+    void* k_base, void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head,
+    const float* k_scale, const float* v_scale,
+    void* out, int64_t o_stride_tok, int64_t o_stride_head,
+    const int64_t* node_kv, const int64_t* node_kv_offset, const int64_t* node_kv_len,
+    const int64_t* node_q, const int64_t* node_q_offset, const int64_t* node_q_len,
+    int NE, int P, int64_t total_kv, int nq, int Hq, int Hkv, int D, float scale,
+    const int32_t* cache_loc, const void* k_new, const void* v_new, int64_t new_stride_tok, int n_new,
+    const void* plan, void* workspace, size_t workspace_bytes, void* stream);
+int deft_node_decode_append_f16_kv8_lse(
+    const void* q, int64_t q_stride_tok, int64_t q_stride_head,
+    void* k_base, void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head,
+    const float* k_scale, const float* v_scale,
+    void* out, int64_t o_stride_tok, int64_t o_stride_head,
+    float* lse, int64_t lse_stride_tok, int64_t lse_stride_head,
+    const int64_t* node_kv, const int64_t* node_kv_offset, const int64_t* node_kv_len,
+    const int64_t* node_q, const int64_t* node_q_offset, const int64_t* node_q_len,
+    int NE, int P, int64_t total_kv, int nq, int Hq, int Hkv, int D, float scale,
+    const int32_t* cache_loc, const void* k_new, const void* v_new, int64_t new_stride_tok, int n_new,
+    const void* plan, void* workspace, size_t workspace_bytes, void* stream);
+/* bfloat16 twin of deft_node_decode_append_f16_kv8_lse */
+int deft_node_decode_append_bf16_kv8_lse(
+    const void* q, int64_t q_stride_tok, int64_t q_stride_head,
+    void* k_base, void* v_base, int64_t kv_stride_slot, int64_t kv_stride_head,
+    const float* k_scale, const float* v_scale,
+    void* out, int64_t o_stride_tok, int64_t o_stride_head,
+    float* lse, int64_t lse_stride_tok, int64_t lse_stride_head,
+    const int64_t* node_kv, const int64_t* node_kv_offset, const int64_t* node_kv_len,
+    const int64_t* node_q, const int64_t* node_q_offset, const int64_t* node_q_len,
+    int NE, int P, int64_t total_kv, int nq, int Hq, int Hkv, int D, float scale,
+    const int32_t* cache_loc, const void* k_new, const void* v_new, int64_t new_stride_tok, int n_new,
     const void* plan, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Quantising paged append: for i < n, head h, k_base[cache_loc[i]][h][:] = e4m3fn(clamp(float(k_new[i][h][:]) / k_scale[h], -448, 448))

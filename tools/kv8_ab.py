@@ -2,13 +2,15 @@
 """The fp16 decode step against the same step over an fp8 KV pool, one process, alternating: the workload's tree
 built twice -- an fp16 pool with N(0,1) data, one distinct KV array per layer, and an fp8 pool that is that pool quantised with unit
 scales -- every layer's call captured in ONE hipGraph per pool type and replayed in turns.  The fp16 call is what bench.py times
-(fused append + attention, one call per layer); the kv8 call is DeFTAttention.forward on the fp8 pool: the quantising append and the
-kv8 operator, two launches per layer.  Beside each, `deft_probe_stream_read` over the kv8 launch's K/V bytes: the ceiling of a launch
+(fused append + attention, one call per layer); the kv8 call is DeFTAttention.forward on the fp8 pool with the quantising append as a
+launch of its own (kv8_fused_append = False: append, kv8 operator); the third arm, "kv8 fused", is the same call with the append inside
+the stage-1 launch (kv8_fused_append = True) -- its outputs and pool bytes are asserted equal to the second arm's.  Beside each, `deft_probe_stream_read` over the kv8 launch's K/V bytes: the ceiling of a launch
 that only reads them.
 
    tools/kv8_ab.py [--workloads northstar_4kx32,gqa_4kx32,tot50_4k,medusa64_node] [--layers 32] [--steps 50] [--reps 7] [--out FILE]
 
-Per workload: per-repetition figures, median and min-max of each, the ratio of the medians."""
+Per workload: per-repetition figures, median and min-max of each arm, the ratios of the medians, and the fused arm's median against the
+two-launch arm's median plus its min-max spread (the routing rule of DESIGN section 6e)."""
 import argparse, os, sys
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -63,7 +65,7 @@ def time_graph(graph, steps, layers):
 
 
 class Step:
-    def __init__(self, w, layers, pool_dtype, source=None):
+    def __init__(self, w, layers, pool_dtype, source=None, fused=None):
         Hq, Hkv, D, _ = GEOMETRY[w.model]
         self.layers = layers
         self.tree, self.pool = build_tree(w, layers, str(dev), dtype=pool_dtype)
@@ -83,6 +85,9 @@ class Step:
         mode = deft_amd.forward_mode_from_cli(w.mode)
         self.meta = deft_amd.InputMetadata(mode, deft_amd.KVCacheUpdater(True, self.pool, loc, None, False), self.pool)
         self.attn = [deft_amd.DeFTAttention(Hq, D, D ** -0.5, Hkv, l) for l in range(layers)]
+        if fused is not None:  # (an fp8 pool: the quantising append inside the stage-1 launch, or as a launch of its own)
+            for at in self.attn:
+                at.kv8_fused_append = fused
         self.graph = capture(self.eager)
         assert bool(torch.isfinite(self.outs[-1]).all())
 
@@ -112,10 +117,14 @@ for name in a.workloads.split(","):
     layers = a.layers or model_layers
     deft_amd.BLOCK_CONFIG["MAX_BLOCK_LEN"] = 128 if w.mode == "node_chunk" else -1
     f16 = Step(w, layers, torch.float16)
-    kv8 = Step(w, layers, FP8, source=f16)
+    kv8 = Step(w, layers, FP8, source=f16, fused=False)
+    kv8f = Step(w, layers, FP8, source=f16, fused=True)
     # the two steps compute the same attention up to the quantisation of K / V: a sanity figure, not a tolerance
     diff = float((f16.outs[-1].float() - kv8.outs[-1].float()).abs().max())
-    runs = {"fp16": f16, "kv8": kv8}
+    # ... and the fused arm is the two-launch arm bit for bit: the last layer's output and every byte of the two pools
+    assert torch.equal(kv8f.outs[-1].view(torch.int16), kv8.outs[-1].view(torch.int16))
+    assert torch.equal(kv8f.pool._storage.view(torch.uint8), kv8.pool._storage.view(torch.uint8))
+    runs = {"fp16": f16, "kv8": kv8, "kv8 fused": kv8f}
     res = {n: [] for n in runs}
     for rep in range(a.reps):
         for n, s in runs.items():
@@ -125,9 +134,13 @@ for name in a.workloads.split(","):
         f"alternating; us per layer")
     for n, xs in res.items():
         say(f"  {n}: " + " ".join(f"{x:.2f}" for x in xs) + f" | median {np.median(xs):.2f} min {np.min(xs):.2f} max {np.max(xs):.2f}")
+    m2, mf = np.median(res["kv8"]), np.median(res["kv8 fused"])
+    spread = np.max(res["kv8"]) - np.min(res["kv8"])
+    say(f"  kv8 fused / kv8 (medians): {mf / m2:.4f}    kv8 fused / fp16: {mf / np.median(res['fp16']):.4f}    fused - two-launch: {mf - m2:+.2f} us, "
+        f"the two-launch arm's min-max spread {spread:.2f} us: {'within' if mf - m2 <= spread else 'BEYOND'} it")
     say(f"  kv8 / fp16 (medians): {np.median(res['kv8']) / np.median(res['fp16']):.4f}    "
         f"bare read of the kv8 launch's {nbytes / 1e6:.1f} MB of K/V: {ceil_us:.2f} us    max |fp16 - kv8| of the last layer: {diff:.3e}")
-    del f16, kv8, runs
+    del f16, kv8, kv8f, runs
     torch.cuda.empty_cache()
 if a.out:
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
