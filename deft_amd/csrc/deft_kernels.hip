@@ -2343,9 +2343,11 @@ int deft_window_patch(int n_nodes, int nq, int nqw, const int32_t* node_start, i
         set_error("deft_window_patch: bad fetch arguments");
         return DEFT_EINVAL;
     }
-    hipLaunchKernelGGL(window_patch_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), t, w,
-                       PageWrite{page_table, page_stride, page_rows, page_cols},
-                       StageFetch{static_cast<const char*>(fetch_ring), static_cast<char*>(fetch_dst), fetch_counter, fetch_slot_bytes, fetch_ring_n});
+    const PageWrite pw{page_table, page_stride, page_rows, page_cols};
+    const StageFetch fetch{static_cast<const char*>(fetch_ring), static_cast<char*>(fetch_dst), fetch_counter, fetch_slot_bytes, fetch_ring_n};
+    // (new_stride_tok = 0: no layer reads k_new / v_new -- the rows are appended by a launch of their own -- and the kernel patches the
+    //  step's rows in as pool rows)
+    hipLaunchKernelGGL(window_patch_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), t, w, pw, fetch);
     return check_launch("window patch launch");
 }
 

@@ -178,7 +178,7 @@ struct WindowPatch {
     const int32_t* pad;        // dims + WIN_DIM_PAD: the live slot a cleared position (row mask 0) aliases
     int max_q_len, G, win_tiles;
     int64_t kv_stride_slot;    // elements
-    int64_t new_row_bytes;
+    int64_t new_row_bytes;     // 0: the layers read no row from k_new / v_new (window_patch_kernel)
 };
 
 // ONE workgroup of 1024 threads per decode step.  Region h of the overflow = the h-th hosting record, chunk by chunk, pass by pass
@@ -189,6 +189,9 @@ struct WindowPatch {
 // (stage_fetch: counter, then header and payload in one round trip) while waves 8-15 walk the device tree -- leaf row -> node -> length, room, last slot: three
 // dependent loads -- and read the overflow runs' record table; one barrier; then the stores.  (13 us -> 8 as one chain after the
 // other, profiles/r6_step_boundary.txt.)
+// A call with new_stride_tok = 0 (w.new_row_bytes == 0: the layers append with a launch of their own and read the step's rows from the
+// POOL -- the two-launch form over an fp8 pool, deft_amd/session.py): an entry's "-1 - new row" becomes the pool offset of
+// cache_loc[row], no record flags a row as new.  The test is on a kernel argument: uniform over the whole launch.
 __global__ __launch_bounds__(1024) void window_patch_kernel(TreeDev t, WindowPatch w, PageWrite pw, StageFetch fetch) {
     __shared__ int sNew[TREE_OPS_NEW], sPos[TREE_OPS_NEW], sMeta[4], sOps[TREE_OPS_LDS];
     __shared__ int sHost[WIN_REGIONS * 2];  // hosting records: (chunk, pass) pairs
@@ -274,12 +277,19 @@ __global__ __launch_bounds__(1024) void window_patch_kernel(TreeDev t, WindowPat
     for (int e = tid; e < n_ent; e += 1024) {
         const int key = ent[3 * e];
         const uint32_t mask = (uint32_t)ent[3 * e + 1];
-        const int val = mask ? ent[3 * e + 2] : pad;  // (a cleared position: no row sees it, but it is read)
+        int val = mask ? ent[3 * e + 2] : pad;  // (a cleared position: no row sees it, but it is read)
         const int hi = key >> 20, pos = key & 0xfffff;
         const int j = pos >> 7, k = pos & (TILE - 1);
         if (hi < 0 || hi >= NH || j >= w.win_tiles) {
             atomicOr(w.err, WIN_ERR);
             continue;
+        }
+        if (w.new_row_bytes == 0 && val < 0) {  // (this step's row: in the pool by the time the layer's attention runs)
+            if (-1 - val >= t.nq) {
+                atomicOr(w.err, WIN_ERR);
+                continue;
+            }
+            val = w.cache_loc[-1 - val];
         }
         const int rec = j == 0 ? sTab[2 * hi] : sTab[2 * hi + 1] + j - 1;
         char* rp = w.records + (int64_t)rec * PLAN_BYTES;

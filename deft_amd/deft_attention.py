@@ -424,7 +424,8 @@ class DeFTAttention(nn.Module):
         it is Node metadata) and PREFILL.  Two launches per layer -- the quantising append (store_kv_cache), then the kv8 operator with
         the layer's per-head scales -- or, with `kv8_fused_append`, the fused operators; a given rotary embedding runs first with its
         own launch.  There is no fused rotary embedding, no extend step and no sequential comparator for fp8 pools: those are
-        refused, never misread as 16-bit."""
+        refused, never misread as 16-bit.  The captured loop over the same pool is `DecodeSession(..., elem_dtype=...)`
+        (deft_amd/session.py): its legacy steps are this call bit for bit, outputs and pool bytes, in either form."""
         mode = input_metadata.forward_mode
         pool = input_metadata.token_to_kv_pool
         if fuse_rope:

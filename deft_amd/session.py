@@ -25,6 +25,15 @@ of window steps are another PARTITION of the same keys than the eager path's: eq
 `incremental=False` is the round-5 loop: bit-identical to the eager path step for step (tests/test_session.py).
 
 DeFT-Flatten and DeFT-Node; head_dim 128, and 64 as head pairs.
+
+fp8 KV pools ("In the captured session"): `elem_dtype` names the 16-bit type of q, the new rows and the outputs; the
+pool's slot stride reaches the plan builders and the patch kernel in 2-byte units (half the byte stride), the layers are the kv8 entry
+points with the layer's per-head scales as DEVICE pointers (read at replay: `set_kv_scales` between two steps needs no new capture).
+Two forms of a layer, `kv8_fused_append`: the fused quantising append (one stage-1 launch; the plan flags the step's rows as "read from
+k_new" exactly as the 16-bit session's does), or the quantising append as a launch of its own in front of the plain kv8 operator -- then
+no row is flagged: legacy plans are built without a cache_loc, and the patch kernel turns a patch entry's "new row" into the pool offset
+of that row's slot (deft_window_patch with new_stride_tok = 0).  Legacy steps of either form are the eager DeFTAttention.forward over
+an fp8 pool bit for bit; window steps write the same pool bytes and agree within the 16-bit session's rules.  head_dim 128 only.
 """
 from __future__ import annotations
 
@@ -33,7 +42,7 @@ from typing import Callable, Dict, List, Optional
 import numpy as np
 import torch
 
-from ._lib import check, elem_suffix, entry, lib, same_elem_dtype
+from ._lib import ELEM_DTYPES, check, elem_suffix, entry, lib, same_elem_dtype
 from .tree_cache import BLOCK_CONFIG, TreeCache, _DeviceTree, _FIELDS, _ptr
 
 __all__ = ["DecodeSession", "FlattenDecodeSession"]
@@ -92,9 +101,18 @@ class DecodeSession:
     EVENT_EVERY = 4  # ... kept from lapping it by an event behind every fourth step (an event per step sits between two captured
                      # graphs and costs the queue idle time: tools/step_boundary.py)
 
+    # fp8 pools: which form of a layer a session runs when `kv8_fused_append` is None -- the fused quantising append (True) or the
+    # append as a launch of its own (False) -- for steps that rebuild the plan (upload / legacy) and for window steps.  The routing rule of
+    # DESIGN section 6e (fused only where it is within the two-launch arm's own spread on EVERY workload) over profiles/kv8_session_cost.txt
+    # (tools/kv8_session_ab.py): legacy steps lose with the fused form on three workloads of four; window steps WIN with it on the three
+    # Flatten workloads (13 % on the north-star tree under Llama-3-8B's heads) and lose 6 % on Medusa-64 Node in every repetition.
+    kv8_fused_append = False
+    kv8_fused_append_window = False
+
     def __init__(self, tree: TreeCache, num_heads: int, num_kv_heads: int, head_dim: int, layers: int,
                  qkv: Callable[[int], tuple], max_q_len: int = 32, use_graph: bool = True, mode: str = "flatten",
-                 capture_after="auto", incremental: bool = True, win_tiles: Optional[int] = None, staging: Optional[str] = None) -> None:
+                 capture_after="auto", incremental: bool = True, win_tiles: Optional[int] = None, staging: Optional[str] = None,
+                 elem_dtype: Optional[torch.dtype] = None, kv8_fused_append: Optional[bool] = None) -> None:
         """`qkv(layer)` -> (q [nq, Hq*D], k_new [nq, Hkv*D], v_new [nq, Hkv*D]) fp16 CUDA tensors at FIXED addresses (the
         model writes this step's projections there); outputs are in `self.out[layer]` ([nq, Hq*D]).
 
@@ -109,11 +127,26 @@ class DecodeSession:
         every token) then stay eager instead of paying a capture per step, and go back to capturing as soon as an epoch lasts.
 
         `incremental`: window plans (module docstring).  `win_tiles`: overflow tiles per query chunk (None: enough for ~16 steps of
-        nq tokens, between 2 and 8)."""
+        nq tokens, between 2 and 8).
+
+        `elem_dtype`: the 16-bit element type of q, the new rows and the outputs.  Required over an fp8 pool (torch.float16 or
+        torch.bfloat16: the pool does not say which; head_dim 128 only); over a 16-bit pool None or the pool's own type.
+        `kv8_fused_append` (fp8 pools; ignored otherwise): True = the fused quantising append, False = the append as a launch of its
+        own in front of the kv8 operator, None = the class defaults (`kv8_fused_append` for steps that rebuild the plan,
+        `kv8_fused_append_window` for window steps)."""
         pool = tree.token_to_kv_pool
-        if getattr(pool, "is_fp8", False):
-            raise NotImplementedError("DecodeSession over an fp8 KV pool is not implemented (no captured steps or window plans for fp8 "
-                                      "pools; run the steps through DeFTAttention.forward)")
+        self.kv8 = bool(getattr(pool, "is_fp8", False))
+        if self.kv8:
+            if elem_dtype is None:
+                raise NotImplementedError("DecodeSession over an fp8 KV pool is not implemented without elem_dtype: pass elem_dtype=torch.float16 "
+                                          "or torch.bfloat16 (the type of q, the new rows and the outputs, which an fp8 pool does not name)")
+            if elem_dtype not in ELEM_DTYPES:
+                raise TypeError(f"DecodeSession: elem_dtype over an fp8 KV pool must be float16 or bfloat16, got {elem_dtype}")
+            if head_dim != 128:
+                raise ValueError(f"DecodeSession: fp8 KV pools are built for head_dim 128 only, got {head_dim}")
+        elif elem_dtype is not None and elem_dtype != pool._storage.dtype:
+            raise TypeError(f"DecodeSession: elem_dtype is {elem_dtype} but the KV pool is {pool._storage.dtype}: over a 16-bit pool q, the new "
+                            "rows and the outputs have the pool's type (pass elem_dtype=None)")
         assert pool.device.type == "cuda" and mode in ("flatten", "node")
         assert head_dim == 128 or (head_dim == 64 and num_kv_heads % 2 == 0), "DecodeSession: head_dim 128, or 64 with an even number of KV heads"
         assert capture_after == "auto" or int(capture_after) >= 1
@@ -137,8 +170,15 @@ class DecodeSession:
         # (the device WITH its index: torch.device("cuda") != torch.device("cuda:0"), and the page-table fold below compares devices --
         #  round 3: with the default "cuda" pool the fold never happened and every step carried an index_put)
         self.tree, self.pool, self.device = tree, pool, pool._storage.device
-        self.dtype = pool._storage.dtype  # the element type of the whole session: q, new rows and outputs share the pool's
+        # the element type of the whole session: q, new rows and outputs share the pool's -- or, over an fp8 pool, are `elem_dtype`
+        self.dtype = elem_dtype if self.kv8 else pool._storage.dtype
         elem_suffix(self.dtype, "the KV pool")
+        if self.kv8:
+            if pool.kv_data[0].stride(0) % 2:
+                raise ValueError("DecodeSession: the fp8 pool's slot stride must be even")
+            # the form of a layer per step kind (class defaults unless the caller forces one form)
+            self.kv8_fused = {"legacy": bool(self.kv8_fused_append if kv8_fused_append is None else kv8_fused_append),
+                              "window": bool(self.kv8_fused_append_window if kv8_fused_append is None else kv8_fused_append)}
         self.Hq, self.Hkv, self.D, self.layers = num_heads, num_kv_heads, head_dim, layers
         self.qkv, self.max_q_len, self.use_graph = qkv, max_q_len, use_graph
         self.graphs: Dict[str, Optional[torch.cuda.CUDAGraph]] = {}
@@ -299,7 +339,51 @@ class DecodeSession:
             table[self.idx[0], self.idx[1]] = self.cache_loc
         return fold
 
-    def _launch_layers(self) -> None:
+    def _slot_stride2(self) -> int:
+        """The pool's slot stride in the 2-byte units the plan builders and the patch kernel count in."""
+        st = self.pool.kv_data[0].stride(0)
+        return st // 2 if self.kv8 else st
+
+    def _new_stride(self, window: bool) -> tuple:
+        """(cache_loc pointer, n_new, new-row stride) a plan of this step is built with: the step's rows flagged as "read from k_new" --
+        the 16-bit session and the fused fp8 form -- or none (the two-launch fp8 form: the rows are in the pool before the attention runs)."""
+        _, k0, _ = self.qkv(0)
+        if self.kv8 and not self.kv8_fused["window" if window else "legacy"]:
+            return None, 0, 0
+        return self.cache_loc.data_ptr(), self.nq, k0.stride(0)
+
+    def _launch_layers_kv8(self, fused: bool) -> None:
+        """The layers over an fp8 pool: byte strides, the layer's scales as device pointers (read when the launch runs)."""
+        Hq, Hkv, D = self.Hq, self.Hkv, self.D
+        kv0 = self.pool.kv_data[0]
+        v_off = kv0.stride(1)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        flat = self.mode == "flatten"
+        if flat:
+            mdl = [self.md_ptrs[k] for k in ("block_q", "block_q_cnts", "block_q_offset", "block_bitmasks", "block_kv", "block_lens")]
+            tail = (self.NB, self.P, self.nq, Hq, Hkv, D, 1.0 / (D ** 0.5))
+        else:
+            mdl = [self.md_ptrs[k] for k in ("node_kv", "node_kv_offset", "node_kv_len", "node_q", "node_q_offset", "node_q_len")]
+            tail = (self.NE, self.PN, self.TKV, self.nq, Hq, Hkv, D, 1.0 / (D ** 0.5))
+        base = "deft_flatten_decode" if flat else "deft_node_decode"
+        fn = entry(base + ("_append{}_kv8" if fused else "{}_kv8"), self.dtype)[0]
+        app = None if fused else entry("deft_kv_append{}_kv8", self.dtype)[0]
+        for l in range(self.layers):
+            q, k, v = self.qkv(l)
+            same_elem_dtype(q=q, k=k, v=v)
+            if q.dtype != self.dtype:
+                raise TypeError(f"q is {q.dtype} but the session's elem_dtype is {self.dtype}")
+            kptr = self.pool.kv_data[l].data_ptr()
+            ks, vs = self.pool.k_scale[l].data_ptr(), self.pool.v_scale[l].data_ptr()
+            new = (self.cache_loc.data_ptr(), k.data_ptr(), v.data_ptr(), k.stride(0), self.nq)
+            if not fused:
+                check(app(kptr, kptr + v_off, kv0.stride(0), kv0.stride(2), ks, vs, *new, Hkv, D, stream), "quantising append")
+            check(fn(q.data_ptr(), q.stride(0), D, kptr, kptr + v_off, kv0.stride(0), kv0.stride(2), ks, vs, self.out[l].data_ptr(), Hq * D, D,
+                     *mdl, *tail, *(new if fused else ()), self.plan.data_ptr(), self.ws.data_ptr(), self.ws_bytes, stream), "decode layer")
+
+    def _launch_layers(self, window: bool = False) -> None:
+        if self.kv8:
+            return self._launch_layers_kv8(self.kv8_fused["window" if window else "legacy"])
         Hq, Hkv, D = self.Hq, self.Hkv, self.D
         kv0 = self.pool.kv_data[0]
         v_off = kv0.stride(1) * 2
@@ -343,12 +427,12 @@ class DecodeSession:
         if self.mode == "flatten":
             mdl = [self.md_ptrs[k] for k in ("block_q", "block_q_cnts", "block_q_offset", "block_bitmasks", "block_kv", "block_lens")]
             check(lib.deft_flatten_build_plan_dims(*mdl, self.NB, self.P, dt.scratch.data_ptr(), Hq, Hkv, q0.stride(0), D,
-                                                   kv0.stride(0), self.cache_loc.data_ptr(), self.nq, k0.stride(0),
+                                                   self._slot_stride2(), *self._new_stride(False),
                                                    self.plan.data_ptr(), self.plan_bytes, stream), "deft_flatten_build_plan_dims")
         else:
             mdl = [self.md_ptrs[k] for k in ("node_kv", "node_kv_offset", "node_kv_len", "node_q", "node_q_offset", "node_q_len")]
             check(lib.deft_node_build_plan_dims(*mdl, self.NE, self.PN, self.TKV, dt.scratch.data_ptr(), Hq, Hkv, q0.stride(0), D,
-                                                kv0.stride(0), self.cache_loc.data_ptr(), self.nq, k0.stride(0),
+                                                self._slot_stride2(), *self._new_stride(False),
                                                 self.plan.data_ptr(), self.plan_bytes, stream), "deft_node_build_plan_dims")
         self._launch_layers()
 
@@ -377,21 +461,22 @@ class DecodeSession:
             if self.mode == "flatten":
                 mdl = [self.md_ptrs[k] for k in ("block_q", "block_q_cnts", "block_q_offset", "block_bitmasks", "block_kv", "block_lens")]
                 check(lib.deft_flatten_build_plan_window(*mdl, self.NB, self.P, dt.scratch.data_ptr(), self.nq, mq, self.W,
-                                                         self.win_tab.data_ptr(), Hq, Hkv, q0.stride(0), D, kv0.stride(0),
+                                                         self.win_tab.data_ptr(), Hq, Hkv, q0.stride(0), D, self._slot_stride2(),
                                                          self.plan.data_ptr(), self.plan_bytes, stream), "deft_flatten_build_plan_window")
             else:
                 mdl = [self.md_ptrs[k] for k in ("node_kv", "node_kv_offset", "node_kv_len", "node_q", "node_q_offset", "node_q_len")]
                 check(lib.deft_node_build_plan_window(*mdl, self.NE, self.PN, self.TKV, dt.scratch.data_ptr(), self.nq, mq, self.W,
-                                                      self.win_tab.data_ptr(), Hq, Hkv, q0.stride(0), D, kv0.stride(0),
+                                                      self.win_tab.data_ptr(), Hq, Hkv, q0.stride(0), D, self._slot_stride2(),
                                                       self.plan.data_ptr(), self.plan_bytes, stream), "deft_node_build_plan_window")
         check(lib.deft_window_patch(*dt._tree_args(), None if replan else self.ops.data_ptr(), self.cache_loc.data_ptr(),
                                     table.data_ptr() if fold else None, table.stride(0) if fold else 0,
                                     self.idx[0].data_ptr() if fold else None, self.idx[1].data_ptr() if fold else None,
                                     self.patch.data_ptr(), self.win_tab.data_ptr(), self.plan.data_ptr(), mq, self.W, Hq, Hkv,
-                                    kv0.stride(0), k0.stride(0), dt.scratch.data_ptr(),
+                                    # (new-row stride 0 -- the two-launch fp8 form -- : a patch entry's new row becomes its slot's pool offset)
+                                    self._slot_stride2(), self._new_stride(True)[2], dt.scratch.data_ptr(),
                                     *((self._ring.data_ptr(), self._ring_slot, self.RING, self._small.data_ptr(), self._ctr.data_ptr())
                                       if folded_fetch else (None, 0, 0, None, None)), stream), "deft_window_patch")
-        self._launch_layers()
+        self._launch_layers(window=True)
 
     # ---- per step ------------------------------------------------------------------------------------------
     def step(self) -> List[torch.Tensor]:

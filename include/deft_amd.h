@@ -976,7 +976,12 @@ int deft_extend_dev_build(const int64_t* t_block_q, const int64_t* t_block_q_cnt
  *                                    a replan step's scan already did), page-table write, the step's slots appended to the device
  *                                    tree, and the host's patch list applied to the plan: int32 {entries, active overflow tiles of
  *                                    regions 0 .. 63, {region << 20 | position, row mask (0 = cleared), pool slot | -1 - new row} ...}
- *                                    (deft_window_step writes it: an entry's row mask is its node's leaf set within the region) */
+ *                                    (deft_window_step writes it: an entry's row mask is its node's leaf set within the region).
+ *                                    kv_stride_slot is in 2-byte units (an fp8 pool: byte stride / 2).  new_stride_tok = 0: the
+ *                                    layers read no row from k_new / v_new (the step's rows are appended by a launch of their own
+ *                                    in front of the attention: deft_kv_append_*_kv8, then the plain *_kv8 call) -- an entry's
+ *                                    "-1 - new row" is then patched in as the pool row of cache_loc[row], and no record flags a row
+ *                                    as new */
 int deft_window_supported(int nq, int max_q_len, int Hq, int Hkv);
 int deft_flatten_build_plan_window(int64_t* block_q, int64_t* block_q_cnts, int64_t* block_q_offset, int64_t* block_bitmasks,
                                    int64_t* block_kv, int64_t* block_lens, int NB, int P, int32_t* dims, int nq, int max_q_len,
